@@ -14,7 +14,15 @@ A generated shape needs 1000 + 1000 such steps, so  value = n_gpus * batch / (10
 synthetic key points, inputs resident in HBM.  N > 1: one process per GPU (torchrun), batch shards are
 independent (weak scaling), one RCCL all-gather of the (B,16,51) latents closes the timed region.
 
-Extra objects on the JSON line:
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the result
+line; `--dump-outputs DIR` also writes the latents of the last timed step as DIR/<name>.npy (float32; inputs are seeded, so
+two builds can be compared output for output).  `--full` adds the reporting legs below (each can still be left out with
+its --no-* option).
+
+Extra objects on the JSON line with --full:
+  parity       forwards of the benched arithmetic and complete chains against the exact-fp32 mode (before the timed region)
+  configs      every BASELINE config timed on its own after the headline
+  decode       the autoencoder-decode leg (BASELINE configs[4])
   roofline     the dominant kernel (the MFMA kernel with the largest share of a feature step's device time): algorithmic
                FLOPs of its launches / their device time, measured with HIP events on the launch stream in an
                instrumented eager replay right after the timed region (the timed region launches without events)
@@ -69,6 +77,22 @@ def cpu_baseline(batch=16, budget_s=25.0):
     return {"value": batch / (1000.0 * sec_per_step), "unit": "shapes/s", "cores": threads, "kind": "port",
             "sample": "numpy/C oracle denoiser forward (pos+feat) at batch %d, %.2f+%.2f s/step (BLAS threads %d of %d host cores), "
                       "extrapolated x1000 steps" % (batch, per["pos"], per["feat"], threads, os.cpu_count())}
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_BYTES_MAX):
+    """`--dump-outputs`: each array as <path>/<name>.npy in float32.  Above `limit` bytes in all, every array keeps the same
+    fixed, seeded sample of its leading-axis rows (in order) -- enough to compare two builds output for output."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrs.values())
+    for k, v in arrs.items():
+        if total > limit and v.shape[0] > 1:
+            keep = max(1, int(v.shape[0] * limit // total))
+            v = v[np.sort(np.random.RandomState(0).choice(v.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def relaunch_argv(gpus, argv, port=None):
@@ -406,6 +430,10 @@ def main():
                     help="default: BASELINE configs[1]+[2] (one position + one feature weight set); five-cat: BASELINE configs[3] -- the "
                          "256 shapes of every GPU are its contiguous shard of a five-category run (labels 0, 2, 3, 4, 6, one weight "
                          "set per category: a chain pair per category segment), latents all-gathered")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the reporting legs (parity, roofline, configs, decode, cpu_baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the latents of the last timed step as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-decode", action="store_true", help="skip the autoencoder-decode leg (BASELINE configs[4]) of the JSON line")
     ap.add_argument("--no-roofline", action="store_true")
@@ -413,6 +441,8 @@ def main():
     ap.add_argument("--no-parity", action="store_true", help="skip the live fp16-vs-fp32 forward error and the fp32-mode timing")
     ap.add_argument("--fp32-steps", type=int, default=10, help="reverse steps of the exact-fp32 mode timed for parity.fp32_mode_shapes_per_s")
     a = ap.parse_args()
+    if not a.full:
+        a.no_cpu_baseline = a.no_decode = a.no_roofline = a.no_configs = a.no_parity = True
     if a.pos_prec is None:
         a.pos_prec = "split" if a.prec == "fp16" else a.prec
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -549,6 +579,9 @@ def main():
     # driver-timed 20-step number carried ~4 ms of that)
     gen = torch.Generator(device=dev)
     gen.manual_seed(1234 + rank)
+    # the parity leg draws from a generator of its own: the timed chains start from the same x_T with or without --full
+    par_gen = torch.Generator(device=dev)
+    par_gen.manual_seed(4321 + rank)
 
     def reset():
         for p_, l_ in pos_chains:
@@ -620,7 +653,7 @@ def main():
     parity_first = os.environ.get("SLIDE_BENCH_PARITY_FIRST", "1") != "0"
     parity_obj = None
     if not a.no_parity and parity_first:  # (every rank checks its own GPU -- and enters the timed region in the same state; rank 0 reports)
-        parity_obj = parity_leg(dev, B, a, pc, fc, sd_p, sd_f, gen)
+        parity_obj = parity_leg(dev, B, a, pc, fc, sd_p, sd_f, par_gen)
         if rank != 0:
             parity_obj = None
     run(max(a.warmup, 1) + max(prime, 0))  # (one replay call: priming steps, then the W warm-up steps)
@@ -688,6 +721,10 @@ def main():
                         "gathered_shapes": int(sum(g_.shape[0] for g_ in gathered))}
     finite = all(bool(torch.isfinite(p_.state()).all().item()) for p_, _ in pos_chains) and \
         all(bool(torch.isfinite(f_.state()).all().item()) for f_, _, _ in feat_chains)
+    if rank == 0 and a.dump_outputs:  # (before the reporting legs: the roofline leg re-begins a feature chain)
+        feats_out = torch.cat(gathered, 0) if use_dist else torch.cat([f_.state().reshape(-1, 16, 51) for f_, _, _ in feat_chains], 0)
+        dump_outputs(a.dump_outputs, {"position_latents": torch.cat([p_.state().reshape(-1, 16, 3) for p_, _ in pos_chains], 0),
+                                      "feature_latents": feats_out})
     ms_per_step = dt * 1e3 / a.steps
     value = world * B / (1000.0 * (ms_per_step / 1e3))
 
@@ -795,7 +832,7 @@ def main():
                                    "achieved_tflops": round(step_fl / (ms_per_step * 1e-3) / 1e12, 1),
                                    "frac": round(step_fl / (ms_per_step * 1e-3) / 1e12 / PEAK_TFLOPS[a.prec], 4)}
     if rank == 0 and not a.no_parity:
-        out["parity"] = parity_obj if parity_obj is not None else parity_leg(dev, B, a, pc, fc, sd_p, sd_f, gen)
+        out["parity"] = parity_obj if parity_obj is not None else parity_leg(dev, B, a, pc, fc, sd_p, sd_f, par_gen)
         out["parity"]["measured"] = "before the timed region" if parity_obj is not None else "after the timed region"
     if rank == 0 and world == 1 and not a.no_configs and a.workload == "default" and a.prec == "fp16":
         try:

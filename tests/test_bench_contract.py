@@ -1,11 +1,13 @@
-"""bench.py's output contract on a GPU box: exactly ONE line on stdout, a JSON object with the driver's keys plus
-`roofline`; the RCCL path (process group, barrier, all-gather, max-over-ranks) is taken in a single-rank run with
-SLIDE_FORCE_DIST=1 -- RCCL writes its banner to the C stdout, which must not reach the JSON stream."""
+"""bench.py's output contract on a GPU box: exactly ONE line on stdout, a JSON object with the driver's keys (plus `roofline`,
+`parity`, `configs`, `decode` with --full; a plain run times the headline only and can dump its outputs); the RCCL path
+(process group, barrier, all-gather, max-over-ranks) is taken in a single-rank run with SLIDE_FORCE_DIST=1 -- RCCL writes its
+banner to the C stdout, which must not reach the JSON stream."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +28,7 @@ def _run(extra_env, *flags):
 
 
 def test_bench_single_json_line(gpu_device):
-    d = _run({})
+    d = _run({}, "--full")
     assert KEYS <= set(d) and d["n_gpus"] == 1 and d["steps"] == 30 and d["scaling"] == "weak" and d["value"] > 0
     assert d["config"]["finite"] and "workload" in d["config"]
     rf = d["roofline"]
@@ -47,6 +49,22 @@ def test_bench_single_json_line(gpu_device):
     assert d["decode"]["shapes_per_s"] > d["decode"]["shapes_per_s_fp32_mode"] > 0 and "parity_test" in d["decode"]
 
 
+def test_bench_plain_run_and_dump_outputs(gpu_device, tmp_path):
+    """a plain run (no --full) is the headline only: no reporting legs on its line; --dump-outputs writes the latents of the
+    last timed step, and two runs with the same arguments start from the same inputs and compute the same latents"""
+    outs = []
+    for k in range(2):
+        d = _run({}, "--dump-outputs", str(tmp_path / ("run%d" % k)))
+        assert KEYS <= set(d) and d["steps"] == 30 and d["warmup"] == 3 and d["config"]["finite"]
+        assert not {"parity", "roofline", "configs", "decode", "cpu_baseline"} & set(d), sorted(d)
+        assert abs(d["value"] - d["config"]["batch_per_gpu"] / d["ms_per_step"]) <= 1e-3 * d["value"]
+        outs.append({n: np.load(str(tmp_path / ("run%d" % k) / (n + ".npy"))) for n in ("position_latents", "feature_latents")})
+    pos_b = d["config"]["batch_per_gpu"] * d["config"]["pos_batch_multiple"]
+    assert outs[0]["position_latents"].shape == (pos_b, 16, 3) and outs[0]["feature_latents"].shape == (256, 16, 51)
+    for n, v in outs[0].items():
+        assert v.dtype == np.float32 and np.isfinite(v).all() and np.array_equal(v, outs[1][n]), n
+
+
 def test_bench_rccl_path_single_rank(gpu_device):
     d = _run({"SLIDE_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29541", "RANK": "0", "WORLD_SIZE": "1",
               "LOCAL_RANK": "0"}, "--no-roofline", "--no-configs")
@@ -56,7 +74,7 @@ def test_bench_rccl_path_single_rank(gpu_device):
 def test_bench_five_category_workload(gpu_device):
     """BASELINE configs[3]: the rank's 256 shapes are five per-category segments, each its own weight set and chain pair;
     the fp32-mode leg of the `parity` object runs beside it (it once borrowed a segment-sized label vector)"""
-    d = _run({}, "--workload", "five-cat", "--no-roofline", "--fp32-steps", "4")
+    d = _run({}, "--workload", "five-cat", "--no-roofline", "--fp32-steps", "4", "--full")
     assert KEYS <= set(d) and d["value"] > 0 and d["config"]["finite"]
     seg = d["config"]["segments_rank0"]
     assert [e["label"] for e in seg] == [0, 2, 3, 4, 6] and sum(e["shapes"] for e in seg) == 256

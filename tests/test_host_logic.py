@@ -159,6 +159,33 @@ def test_bench_self_launch_argv(monkeypatch):
     assert len(calls) == 1 and calls[0][calls[0].index("--nproc-per-node") + 1] == "2" and calls[0][-4:] == ["--gpus", "2", "--steps", "3"]
 
 
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs`: float32 .npy per output; above the size cap every array keeps the same fixed, seeded sample of
+    its rows, within the cap"""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    outs = {"pos": torch.randn(512, 16, 3, generator=g), "feat": torch.randn(256, 16, 51, generator=g).double()}
+    bench.dump_outputs(str(tmp_path / "all"), outs)
+    for k, v in outs.items():
+        got = np.load(str(tmp_path / "all" / (k + ".npy")))
+        assert got.dtype == np.float32 and np.array_equal(got, v.float().numpy())
+    limit = 200000
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), outs, limit=limit)
+    total = 0
+    for k, v in outs.items():
+        a, b = (np.load(str(tmp_path / d / (k + ".npy"))) for d in ("s1", "s2"))
+        assert np.array_equal(a, b) and 0 < a.shape[0] < v.shape[0] and a.shape[1:] == tuple(v.shape[1:])
+        assert all(any(np.array_equal(r, w) for w in v.float().numpy()) for r in a[:3])  # rows of the output, not resampled values
+        total += a.nbytes
+    assert total <= limit
+
+
 @pytest.mark.parametrize("name", ["fp3nn", "bnfirst", "fp3nn_bnfirst", "nobn", "local", "global", "both", "swish_pe_ga", "concat_partial"])
 def test_denoiser_configuration_branches_are_checkpoint_compatible(name):
     """CPU: the module tree PointNet2CloudCondition builds for the non-shipped configuration branches (three-nearest-neighbour FP

@@ -10,7 +10,7 @@ done
 run feat_fused SLIDE_POINT_CHAIN_UPDATE=1 SLIDE_BENCH_ONLY=feat
 run feat_chain SLIDE_POINT_CHAIN_UPDATE=0 SLIDE_BENCH_ONLY=feat
 for v in 1 0; do
-SLIDE_POINT_CHAIN_UPDATE=$v python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-decode --no-parity > $O/roof_pc$v.json 2> $O/roof_pc$v.err
+SLIDE_POINT_CHAIN_UPDATE=$v python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-decode --no-parity > $O/roof_pc$v.json 2> $O/roof_pc$v.err
 python -c "
 import json;d=json.load(open('$O/roof_pc$v.json'));r=d['roofline']
 print('upd$v', d['value'], r['step_ms_eager_sum'], {k:v for k,v in r['mfma_kernels'].items() if 'point' in k})"

@@ -10,7 +10,7 @@ python bench.py --steps 300 --warmup 20 --no-cpu-baseline --no-decode --no-parit
 python bench.py --steps 300 --warmup 20 --no-cpu-baseline --no-decode --no-parity --pos-prec fp16 > $O/bench_300_posfp16.json 2> $O/bench_300_posfp16.err
 SLIDE_BENCH_ONLY=feat python bench.py --steps 300 --warmup 20 --no-cpu-baseline --no-decode --no-parity --no-roofline > $O/bench_300_featonly.json 2> $O/bench_300_featonly.err
 SLIDE_BENCH_ONLY=pos python bench.py --steps 300 --warmup 20 --no-cpu-baseline --no-decode --no-parity --no-roofline > $O/bench_300_posonly.json 2> $O/bench_300_posonly.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o trace -- python bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-parity --no-decode --replay graph > $O/trace_bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o trace -- python bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --no-parity --no-decode --replay graph > $O/trace_bench.log 2>&1
 rm -f $O/trace/*kernel_trace.csv
 timeout 900 python -m pytest tests/test_hip_engine.py -q -m gpu -k "benched or optin or smoke" > $O/gputest_subset.log 2>&1
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1

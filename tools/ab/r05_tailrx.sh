@@ -14,7 +14,7 @@ for v in 2 1 0; do
 run feat_rx$v SLIDE_TAIL_RX=$v SLIDE_BENCH_ONLY=feat
 done
 for v in 2 1 0; do
-SLIDE_TAIL_RX=$v python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-decode --no-parity > $O/roof_rx$v.json 2> $O/roof_rx$v.err
+SLIDE_TAIL_RX=$v python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-decode --no-parity > $O/roof_rx$v.json 2> $O/roof_rx$v.err
 python -c "
 import json;d=json.load(open('$O/roof_rx$v.json'));r=d['roofline']
 print('rx$v', d['value'], r['frac'], r['step_ms_eager_sum'], {k:v for k,v in r['mfma_kernels'].items() if 'tail' in k})"

@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r06_b1; mkdir -p $O
-( time python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench20.json 2> $O/bench20.err ) 2> $O/time.txt
+( time python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench20.json 2> $O/bench20.err ) 2> $O/time.txt
 tail -3 $O/time.txt; tail -5 $O/bench20.err
 python - <<'PY'
 import json

@@ -3,6 +3,6 @@ bash tools/rocprof_run6.sh r06a > $O/prof.log 2>&1; tail -8 $O/prof.log
 bash tools/rocprof_modules.sh r06 > $O/profm.log 2>&1; tail -4 $O/profm.log
 bash tools/decode_hbm.sh r06 > $O/dechbm.log 2>&1; tail -2 $O/dechbm.log
 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r06_bench_default_steps20.json 2> $O/bench20.err; cut -c1-200 $O/r06_bench_default_steps20.json
-python bench.py > $O/r06_bench_default_noflags.json 2> $O/bench.err; cut -c1-200 $O/r06_bench_default_noflags.json
-python bench.py --workload five-cat --steps 100 --warmup 10 --no-cpu-baseline --no-decode > $O/r06_bench_five_cat.json 2> $O/bench5.err; cut -c1-200 $O/r06_bench_five_cat.json
+python bench.py --full > $O/r06_bench_default_noflags.json 2> $O/bench.err; cut -c1-200 $O/r06_bench_default_noflags.json
+python bench.py --full --workload five-cat --steps 100 --warmup 10 --no-cpu-baseline --no-decode > $O/r06_bench_five_cat.json 2> $O/bench5.err; cut -c1-200 $O/r06_bench_five_cat.json
 du -sh gpurun_out/prof_r06a gpurun_out/prof_r06a_pos gpurun_out/prof_r06a_curve gpurun_out/profm_r06 gpurun_out/dechbm_r06

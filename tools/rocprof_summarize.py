@@ -25,7 +25,7 @@ def short(n):
 
 rows = list(csv.DictReader(open(os.path.join(src, "trace", "trace_kernel_stats.csv"))))
 with open(os.path.join(dst, tag + "_kernel_stats.md"), "w") as f:
-    f.write("# rocprofv3 --kernel-trace --stats (%s): `python bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-parity --no-decode --replay graph` (graph replay: not host-bound under the profiler)\n\n" % tag)
+    f.write("# rocprofv3 --kernel-trace --stats (%s): `python bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --no-parity --no-decode --replay graph` (graph replay: not host-bound under the profiler)\n\n" % tag)
     bl = os.path.join(src, "bench.log")
     if os.path.exists(bl):
         for line in open(bl):

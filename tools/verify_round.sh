@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/final; O=gpurun_out/final; T=${1:-r06c}
 python -m pytest tests -m gpu -q 2>&1 | tail -8 > $O/final_gputest.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/final_smoke.log 2>&1
 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${T}_bench_default_steps20.json 2> $O/final_bench20.err
-python bench.py > $O/${T}_bench_default_noflags.json 2> $O/final_bench.err
+python bench.py --full > $O/${T}_bench_default_noflags.json 2> $O/final_bench.err
 python bench.py --steps 100 --warmup 10 --workload five-cat --no-cpu-baseline --no-decode --no-parity --no-roofline --no-configs > $O/${T}_bench_five_cat.json 2> $O/final_bench5.err
 if [ -f build_tmp/libbase0.so ]; then bash tools/ab/r06_libab.sh base0 3 > $O/${T}_ab_base0.txt 2>&1; fi
 for b in 88 688; do python tools/profile_ops.py --batch $b 2>&1 | grep -v amdgpu.ids > $O/${T}_ops_$b.txt; done
