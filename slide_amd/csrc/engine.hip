@@ -1752,6 +1752,9 @@ __global__ __launch_bounds__(256) void finalize_gn_kernel(int B, int C, int bs, 
   const int g = gid[c];
   float sc = 1.f, sh = 0.f;
   if (g >= 0) {
+    // no FMA contraction: the small-launch GEMM that finalises the statistics itself (gemm_small.h) must round the same
+    // operations the same way -- a one-ulp difference of a scale flips its fp16 rounding in a few samples
+#pragma clang fp contract(off)
     float S = 0.f, SS = 0.f;
     for (int cc = gstart[g]; cc < gend[g]; ++cc) {
       S += sum[(size_t)b * bs + cc];

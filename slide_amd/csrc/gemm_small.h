@@ -114,6 +114,7 @@ __device__ __forceinline__ void small_body(const GemmArgs &a, const PairArgs &pa
         b = b < nb ? b : nb - 1;
         float mean = 0.f, rstd = 0.f;
         if (g < f.G) {
+#pragma clang fp contract(off)  // (bit-equal to finalize_gn_kernel: the plan uses either, depending on the batch size)
           float S = 0.f, SS = 0.f;
           // sixteen channels per trip as four 16-byte loads per array (dword-aligned: a group starts at any channel), all
           // issued together: the 128 threads' scattered 4-byte loads made a trip cost ~1.2 us (request rate), and a 24-channel
@@ -168,6 +169,7 @@ __device__ __forceinline__ void small_body(const GemmArgs &a, const PairArgs &pa
           const int g = gq[u];
           float sc = 1.f, sh = 0.f;
           if (g >= 0) {
+#pragma clang fp contract(off)
             sc = gm[u] * grp[(sm * 32 + g) * 2 + 1];
             sh = bt[u] - grp[(sm * 32 + g) * 2] * sc;
           }

@@ -77,30 +77,52 @@ def test_optin_fp16_position_plan_is_bounded(gpu_device):
     assert worst <= 4e-3, worst
 
 
+_BENCHED_FEATURE_LAUNCH = {}  # B -> (oracle, fp32 engine, fp16 plan) outputs, shared by the two tests below
+
+
+def _benched_feature_launch(gpu_device, B):
+    if B not in _BENCHED_FEATURE_LAUNCH:
+        from oracle import denoiser_np as D
+        from slide_amd.engine import DenoiserEngine
+        from slide_amd.synth import synth_keypoints
+        g, hp, sd = _load("feat")
+        rs = np.random.RandomState(B)
+        x = rs.standard_normal((B, 16, 51)).astype(np.float32)
+        x[:, :, :3] = synth_keypoints(B, seed=B)
+        ts = rs.randint(0, 1000, B).astype(np.float32)
+        label = rs.randint(0, 13, B).astype(np.int64)
+        ref = np.concatenate([D.denoiser_forward(hp, sd, x[i:i + 32], ts[i:i + 32], label[i:i + 32]) for i in range(0, B, 32)])
+        y32 = DenoiserEngine(hp, sd, B, gpu_device, prec="fp32").forward(x, ts, label).cpu().numpy()
+        y16 = DenoiserEngine(hp, sd, B, gpu_device, prec="fp16").forward(x, ts, label).cpu().numpy()
+        _BENCHED_FEATURE_LAUNCH[B] = (ref, y32, y16)
+    return _BENCHED_FEATURE_LAUNCH[B]
+
+
 @pytest.mark.parametrize("B", [88, 256])
 def test_feature_denoiser_at_the_benched_launch_sizes_matches_oracle(gpu_device, B):
     """the goldens hold 2-3 samples; the benched launches hold 88 / 80 samples per feature sub-batch (and 256 in
     the single-chain arrangement) -- other tile maps, XCD groups, grid-size dependent kernel choices.  The exact-fp32 engine
     against the numpy oracle at those sizes (<= 2e-4 of the output's max, as at golden size), and the fp16 throughput plan
-    against the same oracle output (<= 1e-3 relative L2, the single-forward criterion)."""
-    from oracle import denoiser_np as D
-    from slide_amd.engine import DenoiserEngine
-    from slide_amd.synth import synth_keypoints
-    g, hp, sd = _load("feat")
-    rs = np.random.RandomState(B)
-    x = rs.standard_normal((B, 16, 51)).astype(np.float32)
-    x[:, :, :3] = synth_keypoints(B, seed=B)
-    ts = rs.randint(0, 1000, B).astype(np.float32)
-    label = rs.randint(0, 13, B).astype(np.int64)
-    ref = np.concatenate([D.denoiser_forward(hp, sd, x[i:i + 32], ts[i:i + 32], label[i:i + 32]) for i in range(0, B, 32)])
-    y32 = DenoiserEngine(hp, sd, B, gpu_device, prec="fp32").forward(x, ts, label).cpu().numpy()
+    against the same oracle output (<= 1e-3 relative L2, the single-forward criterion; its max-norm: the test below)."""
+    ref, y32, y16 = _benched_feature_launch(gpu_device, B)
     assert np.isfinite(y32).all() and _rel(y32, ref) <= 2e-4, _rel(y32, ref)
-    y16 = DenoiserEngine(hp, sd, B, gpu_device, prec="fp16").forward(x, ts, label).cpu().numpy()
     r16 = float(np.linalg.norm(y16 - ref) / np.linalg.norm(ref))
     per = np.linalg.norm((y16 - ref).reshape(B, -1), axis=1) / np.linalg.norm(ref.reshape(B, -1), axis=1)
-    print("feature net, B = %d: fp32 engine vs oracle %.2e (max-norm); fp16 plan vs oracle %.2e relative L2 (per sample: median %.2e, max %.2e)"
-          % (B, _rel(y32, ref), r16, np.median(per), per.max()))
+    print("feature net, B = %d: fp32 engine vs oracle %.2e (max-norm); fp16 plan vs oracle %.2e relative L2 (per sample: median %.2e, "
+          "max %.2e), max-norm %.2e" % (B, _rel(y32, ref), r16, np.median(per), per.max(), _rel(y16, ref)))
     assert np.isfinite(y16).all() and r16 <= 1e-3, r16
+
+
+@pytest.mark.parametrize("B", [pytest.param(88, marks=pytest.mark.xfail(strict=True, reason=(
+    "fp16 feature plan, max-norm vs the oracle at 88 samples: 1.46e-3 measured (relative L2 5.8e-4).  Form A, the same kernels "
+    "as at 256 samples (7.4e-4), and every large-batch form computes the same samples bit for bit: the fp16 operand arithmetic, "
+    "not a kernel -- single forwards meet 1e-3 in the L2 norm, not in the max-norm of every batch"))), 256])
+def test_feature_fp16_plan_max_norm_at_the_benched_launch_sizes(gpu_device, B):
+    """north_star's 1e-3 in the max-norm (max |difference| / max |oracle|) of the benched fp16 feature plan over a whole benched
+    launch, as test_benched_arithmetic_meets_1e3_on_reference_goldens asserts it on the 2-3-sample goldens"""
+    ref, _, y16 = _benched_feature_launch(gpu_device, B)
+    print("feature net, B = %d: fp16 plan vs oracle max-norm %.2e" % (B, _rel(y16, ref)))
+    assert _rel(y16, ref) <= 1e-3, _rel(y16, ref)
 
 
 def test_position_denoiser_at_the_benched_launch_size_matches_oracle(gpu_device):
@@ -123,8 +145,10 @@ def test_position_denoiser_at_the_benched_launch_size_matches_oracle(gpu_device)
         assert np.isfinite(y32).all() and _rel(y32, ref) <= 2e-4, (fam, _rel(y32, ref))
         y16 = e16.forward(x, ts, label).cpu().numpy()
         r16 = float(np.linalg.norm(y16 - ref) / np.linalg.norm(ref))
-        print("position net, B = 256, %s inputs: fp32 engine vs oracle %.2e; benched (split) plan vs oracle %.2e relative L2" % (fam, _rel(y32, ref), r16))
-        assert np.isfinite(y16).all() and r16 <= 1e-3, (fam, r16)
+        m16 = _rel(y16, ref)
+        print("position net, B = 256, %s inputs: fp32 engine vs oracle %.2e; benched (split) plan vs oracle %.2e relative L2, %.2e max-norm"
+              % (fam, _rel(y32, ref), r16, m16))
+        assert np.isfinite(y16).all() and r16 <= 1e-3 and m16 <= 2e-4, (fam, r16, m16)
 
 
 def test_denoiser_larger_batch_matches_oracle(gpu_device):
@@ -153,11 +177,15 @@ def test_denoiser_larger_batch_matches_oracle(gpu_device):
 def test_ragged_batches_through_the_fp16_plan(gpu_device, name):
     """Batch sizes that leave row tiles and XCD groups partly empty (1, 5, 17, 100 samples: 16-row GEMM tiles of 64 rows,
     256-row tiles of one or two samples, eight-tile XCD groups) through the default fp16 plan -- pair tables, generated-X
-    GEMMs, fused chains, dual launch -- against the exact fp32 engine at the same batch: <= 5e-3 relative L2 (measured 7e-4)."""
+    GEMMs, fused chains, dual launch -- against the exact fp32 engine at the same batch.  Feature net (the benched fp16 plan):
+    north_star's 1e-3 in the relative L2 norm and the max-norm (measured <= 4.9e-4 / 7.4e-4).  Position net: the opt-in fp16 plan
+    (not benched; its single forwards miss 1e-3, test_optin_fp16_position_plan_is_bounded): <= 2e-3 / 4e-3 (measured 1.0e-3 /
+    1.4e-3 at one sample)."""
     from slide_amd.engine import DenoiserEngine
     g, hp, sd = _load(name)
     rs = np.random.RandomState(4)
     C = g["x_t0"].shape[2]
+    tol_l2, tol_max = (1e-3, 1e-3) if name == "feat" else (2e-3, 4e-3)
     for B in (1, 5, 17, 100):
         x = rs.standard_normal((B, 16, C)).astype(np.float32)
         ts = rs.randint(0, 1000, B).astype(np.float32)
@@ -165,15 +193,18 @@ def test_ragged_batches_through_the_fp16_plan(gpu_device, name):
         y16 = DenoiserEngine(hp, sd, B, gpu_device, prec="fp16").forward(x, ts, label).cpu().numpy()
         y32 = DenoiserEngine(hp, sd, B, gpu_device, prec="fp32").forward(x, ts, label).cpu().numpy()
         rel = float(np.linalg.norm(y16 - y32) / np.linalg.norm(y32))
-        assert np.isfinite(y16).all() and rel <= 5e-3, (B, rel)
+        print("%s net, fp16 plan vs fp32 engine, B = %d: relative L2 %.2e, max-norm %.2e" % (name, B, rel, _rel(y16, y32)))
+        assert np.isfinite(y16).all() and rel <= tol_l2 and _rel(y16, y32) <= tol_max, (B, rel, _rel(y16, y32))
 
 
 @pytest.mark.parametrize("name", ["pos", "feat"])
 def test_full_size_properties(gpu_device, name):
     """BASELINE batch (256 per GPU, and the 128-sample sub-batches the bench replays): size-independent properties.
-    (1) fp16 throughput mode vs fp32 parity mode of the same engine: <= 5e-3 relative L2;
+    (1) fp16 throughput mode vs fp32 parity mode of the same engine: feature net (benched) <= 1e-3 relative L2 and max-norm
+        (measured 4.7e-4 / 7.0e-4); position net (opt-in fp16 plan) <= 2e-3 / 4e-3 (measured 1.1e-3 / 2.6e-3);
     (2) sample independence at full size: a sample's output does not depend on where in the batch it sits, nor on the
-        batch size it is launched with (256 vs 128 -- different tile shapes / kernel variants per launch);
+        batch size it is launched with (256 vs 128: the same plan form, other grids and tile occupancy) -- bit for bit
+        (the batch sizes that change the kernels: test_feature_plan_forms_agree_on_the_same_samples);
     (3) determinism of repeated launches."""
     from slide_amd.engine import DenoiserEngine
     g, hp, sd = _load(name)
@@ -189,14 +220,149 @@ def test_full_size_properties(gpu_device, name):
     e32 = DenoiserEngine(hp, sd, B, gpu_device, prec="fp32")
     y32 = e32.forward(x, ts, label).cpu().numpy()
     rel = float(np.linalg.norm(y16 - y32) / np.linalg.norm(y32))
-    assert rel <= 5e-3, rel
     perm = rs.permutation(B)
     yp = e16.forward(x[perm], ts[perm], label[perm]).cpu().numpy()
-    # per-sample arithmetic is identical wherever the sample sits (GroupNorm statistics are per sample)
-    assert np.abs(yp - y16[perm]).max() <= 2e-3 * np.abs(y16).max()
     eh = DenoiserEngine(hp, sd, 128, gpu_device, prec="fp16")
     yh = eh.forward(x[:128], ts[:128], label[:128]).cpu().numpy()
-    assert np.abs(yh - y16[:128]).max() <= 2e-3 * np.abs(y16).max()
+    print("%s net, B = 256: fp16 vs fp32 relative L2 %.2e, max-norm %.2e; permuted: equal %s (%.2e); 128 vs 256: equal %s (%.2e)"
+          % (name, rel, _rel(y16, y32), np.array_equal(yp, y16[perm]), _rel(yp, y16[perm]), np.array_equal(yh, y16[:128]),
+             _rel(yh, y16[:128])))
+    tol_l2, tol_max = (1e-3, 1e-3) if name == "feat" else (2e-3, 4e-3)
+    assert rel <= tol_l2 and _rel(y16, y32) <= tol_max, (rel, _rel(y16, y32))
+    # per-sample arithmetic is identical wherever the sample sits (GroupNorm statistics are per sample)
+    assert np.array_equal(yp, y16[perm]), _rel(yp, y16[perm])
+    assert np.array_equal(yh, y16[:128]), _rel(yh, y16[:128])
+
+
+def _oracle_subset(B, seed=0):
+    """the samples of a batch of B that the host oracle evaluates: the first 8 and the last 8 (the part-filled last tile), the
+    first sample of each eighth of the batch (XCD group boundaries) and 24 seeded random others"""
+    pick = set(range(min(8, B))) | set(range(max(0, B - 8), B)) | {(k * B) // 8 for k in range(8)}
+    rs = np.random.RandomState(1000 + B + seed)
+    return np.array(sorted(pick | set([int(i) for i in rs.permutation(B) if int(i) not in pick][:24])))
+
+
+def _oracle_rows(hp, sd, x, ts, label, idx):
+    """oracle/denoiser_np.py on the samples idx only: the network is per sample (GroupNorm statistics are per sample)"""
+    from oracle import denoiser_np as D
+    return np.concatenate([D.denoiser_forward(hp, sd, x[idx[i:i + 16]], ts[idx[i:i + 16]], label[idx[i:i + 16]])
+                           for i in range(0, len(idx), 16)])
+
+
+def _per_sample_max(y, ref):
+    """max |difference| / max |reference| of every sample"""
+    n = y.shape[0]
+    return np.abs(y - ref).reshape(n, -1).max(axis=1) / np.abs(ref).reshape(n, -1).max(axis=1)
+
+
+def _inputs(B, cx, seed, family="normal"):
+    """x ~ N(0, 1) with the key-point channels from synth_keypoints (family "keypoints": the coordinates alone are key points),
+    timesteps over [0, 1000), random labels"""
+    from slide_amd.synth import synth_keypoints
+    rs = np.random.RandomState(seed)
+    x = rs.standard_normal((B, 16, cx)).astype(np.float32)
+    if family == "keypoints" or cx > 3:
+        x[:, :, :3] = synth_keypoints(B, seed=seed)
+    return x, rs.randint(0, 1000, B).astype(np.float32), rs.randint(0, 13, B).astype(np.int64)
+
+
+# fp16 feature plan, batch sizes of forms B - F (tests/plan_forms.py): both sides of the 64- / 128-channel tile switch, the three
+# feature sub-batch sizes of `bench.py --batch 1024 / 2048 / 4096` (344; 688; 1365 and 1364 share form D / E with 1025 / 1365),
+# the first size with a separate finalise launch per threshold
+FORM_SIZES = [257, 344, 513, 688, 1025, 1365, 2049]
+
+
+@pytest.mark.parametrize("B", FORM_SIZES)
+def test_every_feature_plan_form_matches_oracle(gpu_device, B):
+    """The fp16 feature plan's kernels depend on the batch size (tests/plan_forms.py); the default selections otherwise never build
+    it above 256 samples.  At a representative size of every large-batch form, on the oracle subset (_oracle_subset): the
+    exact-fp32 engine within 2e-4 of the oracle in the max-norm of EVERY sample, and the fp16 plan within north_star's 1e-3 in the
+    relative L2 norm and in the max-norm over the subset."""
+    from plan_forms import expected_feature_fp16_signature, feature_fp16_form, form_signature
+    from slide_amd.engine import DenoiserEngine
+    _, hp, sd = _load("feat")
+    x, ts, lab = _inputs(B, 51, seed=B)
+    e16 = DenoiserEngine(hp, sd, B, gpu_device, prec="fp16")
+    assert form_signature(e16) == expected_feature_fp16_signature(B), (B, form_signature(e16))
+    idx = _oracle_subset(B)
+    ref = _oracle_rows(hp, sd, x, ts, lab, idx)
+    y16 = e16.forward(x, ts, lab).cpu().numpy()
+    del e16
+    y32 = DenoiserEngine(hp, sd, B, gpu_device, prec="fp32").forward(x, ts, lab).cpu().numpy()
+    assert np.isfinite(y16).all() and np.isfinite(y32).all()
+    p32 = _per_sample_max(y32[idx], ref)
+    p16 = _per_sample_max(y16[idx], ref)
+    l2 = float(np.linalg.norm(y16[idx] - ref) / np.linalg.norm(ref))
+    mx = _rel(y16[idx], ref)
+    print("feature net, form %s, B = %d (%d samples vs oracle): fp32 engine per-sample max-norm median %.2e, max %.2e; "
+          "fp16 plan relative L2 %.2e, max-norm %.2e (per sample: median %.2e, max %.2e at sample %d)"
+          % (feature_fp16_form(B), B, len(idx), np.median(p32), p32.max(), l2, mx, np.median(p16), p16.max(), idx[p16.argmax()]))
+    assert p32.max() <= 2e-4, (B, p32.max(), idx[p32.argmax()])
+    assert l2 <= 1e-3 and mx <= 1e-3, (B, l2, mx)
+
+
+def test_feature_plan_forms_agree_on_the_same_samples(gpu_device):
+    """The same 48 samples inside batches of every fp16 feature plan form (256: form A; FORM_SIZES: forms B - F), at different
+    positions among seeded other samples.  The forms differ in launch fusion (dual launch, query GEMM riding on the SA chain, the
+    GroupNorm finalisation inside the 16-row GEMM or as its own launch) and in the width of the generated-X tiles, never in the
+    arithmetic of a sample: every sample's output is the same bits in every form.  (Before the two GroupNorm finalisations were
+    compiled without FMA contraction, 4 of these 48 samples differed by up to 7.0e-4 between the fused and the separate one.)"""
+    from plan_forms import feature_fp16_form
+    from slide_amd.engine import DenoiserEngine
+    _, hp, sd = _load("feat")
+    n = 48
+    xs, tss, labs = _inputs(n, 51, seed=4242)
+    outs = {}
+    for B in [256] + FORM_SIZES:
+        x, ts, lab = _inputs(B, 51, seed=5000 + B)
+        pos = np.sort(np.random.RandomState(B).choice(B, n, replace=False))
+        pos[0], pos[-1] = 0, B - 1  # the first tile and the part-filled last one
+        perm = np.random.RandomState(B + 1).permutation(n)
+        x[pos], ts[pos], lab[pos] = xs[perm], tss[perm], labs[perm]
+        y = DenoiserEngine(hp, sd, B, gpu_device, prec="fp16").forward(x, ts, lab).cpu().numpy()
+        assert np.isfinite(y).all()
+        out = np.empty((n,) + y.shape[1:], y.dtype)
+        out[perm] = y[pos]
+        outs[B] = out
+    a = outs[256]
+    diffs = {}
+    for B in FORM_SIZES:
+        d = _per_sample_max(outs[B], a)
+        diffs[B] = (bool(np.array_equal(outs[B], a)), float(d.max()))
+        print("form %s (B = %d) vs form A (B = 256), 48 samples: bit-identical %s, per-sample max-norm max %.2e, median %.2e"
+              % (feature_fp16_form(B), B, diffs[B][0], d.max(), np.median(d)))
+    for B in FORM_SIZES:
+        assert diffs[B][0], (B, diffs[B])
+
+
+@pytest.mark.parametrize("B", [512, 4096])
+def test_position_split_plan_at_and_above_the_benched_launch_size(gpu_device, B):
+    """The benched position chain runs the split plan at 512 samples per launch (`pos_batch_multiple: 2`); 4096 covers `--batch
+    4096`'s sub-batches and beyond.  The split plan is one form at every size (tests/plan_forms.py), fp32-grade: on the oracle
+    subset -- plus the sample where the split plan and the exact-fp32 engine differ most -- <= 2e-4 in every sample's max-norm
+    (measured <= 1.4e-5), and within 2e-5 (max-norm) of the exact-fp32 engine at the same batch for both input families (chain
+    start N(0, 1); chain end key-point-like coordinates) at 512 (measured 7.7e-6); 4096 key-point-like samples reach 2.6e-5
+    (two fp32-grade summation orders, the worst of 4096 samples; both engines stay within 1.3e-5 of the oracle on the
+    subset): 5e-5 there."""
+    from slide_amd.engine import DenoiserEngine
+    _, hp, sd = _load("pos")
+    e32 = DenoiserEngine(hp, sd, B, gpu_device, prec="fp32")
+    esp = DenoiserEngine(hp, sd, B, gpu_device, prec="split")
+    for fam in ("normal", "keypoints"):
+        x, ts, lab = _inputs(B, 3, seed=B + 7, family=fam)
+        y32 = e32.forward(x, ts, lab).cpu().numpy()
+        ysp = esp.forward(x, ts, lab).cpu().numpy()
+        assert np.isfinite(y32).all() and np.isfinite(ysp).all()
+        worst = int(np.abs(ysp - y32).reshape(B, -1).max(axis=1).argmax())
+        idx = np.union1d(_oracle_subset(B), [worst])
+        ref = _oracle_rows(hp, sd, x, ts, lab, idx)
+        psp = _per_sample_max(ysp[idx], ref)
+        p32 = _per_sample_max(y32[idx], ref)
+        vs32 = _rel(ysp, y32)
+        print("position net, B = %d, %s inputs: split plan vs oracle per-sample max-norm median %.2e, max %.2e (fp32 engine %.2e); "
+              "split vs fp32 engine %.2e (sample %d)" % (B, fam, np.median(psp), psp.max(), p32.max(), vs32, worst))
+        assert psp.max() <= 2e-4 and p32.max() <= 2e-4, (fam, psp.max(), p32.max())
+        assert vs32 <= (2e-5 if B <= 512 else 5e-5), (fam, vs32)
 
 
 def _pos_cfg():
@@ -889,3 +1055,27 @@ def test_position_sampler_full_chain_fp16_matches_reference(gpu_device):
     r = _rel(smp.sample(g["label"], xT).cpu().numpy(), g["full_x0"])
     print("1000-step position chain in fp16, relative max error vs reference: %.3e" % r)
     assert r <= 1e-3, r
+
+
+def test_feature_chain_at_a_form_c_sub_batch_follows_the_fp32_chain(gpu_device):
+    """north_star's criterion on generated latents in the feature sub-batch size of `bench.py --batch 2048` (688 shapes: form C of
+    the fp16 plan -- 128-channel generated-X tiles, the SA chain apart from its query GEMM, a separate GroupNorm finalise launch):
+    one complete 1000-step chain in the benched fp16 arithmetic against the exact-fp32 chain, equal in-kernel seeds, <= 1e-3 per
+    shape; batch statistics must agree."""
+    from plan_forms import FEATURE_FP16_FORMS, feature_fp16_form, form_signature
+    from slide_amd.diffusion import FeatureSampler
+    import time
+    B = 688
+    assert feature_fp16_form(B) == "C"
+    g, hp, sd = _load("feat")
+    cfg = json.loads(str(load_golden("golden_sampler_feat.npz")["config_json"]))
+    fs = FeatureSampler(hp, sd, B, gpu_device, cfg, prec="fp16", seed=78, use_graph=False)
+    sig = form_signature(fs.engine)
+    assert sig[2] == FEATURE_FP16_FORMS["C"][2][2] and sig[1]["OP_FINALIZE_GN"] == 1, sig  # (sampler mode: no t-embedding launch)
+    del fs
+    t0 = time.time()
+    res = _full_chains(gpu_device, B, {"bench": (None, "fp16"), "fp32": (None, "fp32")})
+    print("688-shape feature chains (fp16 + fp32): %.1f s" % (time.time() - t0))
+    per_shape, dm, ratio = _chain_agreement("feat", res["feat", "bench"], res["feat", "fp32"], B)
+    assert per_shape.max() <= 1e-3, (int((per_shape > 1e-3).sum()), per_shape.max())
+    assert dm.max() <= 0.01 and 0.99 <= ratio.min() and ratio.max() <= 1.01

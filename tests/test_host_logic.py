@@ -204,3 +204,30 @@ def test_denoiser_configuration_branches_are_checkpoint_compatible(name):
     net = PointNet2CloudCondition(hp)
     assert {k: tuple(v.shape) for k, v in net.state_dict().items()} == dict(golden_spec(g, name + "_spec"))
     assert g[name + "_eps"].shape == (2, 16, 6 if name == "swish_pe_ga" else 3) and np.isfinite(g[name + "_eps"]).all()
+
+
+def test_batch_size_plan_forms():
+    """the plan's kernels depend on the batch size (tests/plan_forms.py): the fp16 feature plan's six forms on both sides of every
+    threshold; the split position plan and the fp32 plans are one form at every size.  A moved threshold fails here -- move the
+    representative sizes of tests/test_hip_engine.py::test_every_feature_plan_form_matches_oracle with it."""
+    from plan_forms import FEATURE_FP16_FORMS, expected_feature_fp16_signature, feature_fp16_form, form_signature
+    from slide_amd.engine import DenoiserEngine
+    from slide_amd.synth import synth_state_dict
+    cpu = torch.device("cpu")
+    hp = configs.feature_ddpm_config()["pointnet_config"]
+    sd = synth_state_dict(model_spec.denoiser_param_spec(hp))
+    seen = set()
+    for B in (1, 256, 257, 512, 513, 1024, 1025, 1364, 1365, 2048, 2049):
+        sig = form_signature(DenoiserEngine(hp, sd, B, cpu, prec="fp16"))
+        assert sig == expected_feature_fp16_signature(B), (B, feature_fp16_form(B), sig)
+        seen.add(feature_fp16_form(B))
+    assert seen == set(FEATURE_FP16_FORMS)
+    assert len({str(f[2]) for f in FEATURE_FP16_FORMS.values()}) == len(FEATURE_FP16_FORMS)  # six distinct forms
+    sig32 = [form_signature(DenoiserEngine(hp, sd, B, cpu, prec="fp32")) for B in (1, 2049)]
+    assert sig32[0] == sig32[1] and sig32[0][0] == 50
+    php = configs.position_ddpm_config()["pointnet_config"]
+    psd = synth_state_dict(model_spec.denoiser_param_spec(php))
+    sigs = [form_signature(DenoiserEngine(php, psd, B, cpu, prec="split")) for B in (1, 256, 512, 4096)]
+    assert all(s == sigs[0] for s in sigs) and sigs[0][0] == 29, sigs
+    sig32 = [form_signature(DenoiserEngine(php, psd, B, cpu, prec="fp32")) for B in (1, 4096)]
+    assert sig32[0] == sig32[1] and sig32[0][0] == 50
