@@ -549,6 +549,7 @@ __device__ __forceinline__ void glds_tile(const GemmArgs &a, unsigned char *smem
   }
   const _Float16 *const aff_w = aff_lds + (size_t)((wave * 64) >> NPXL) * 3 * a.k_pad;  // this wave's sample
   const bool aff_relu = AFF && a.aff_relu;
+  const bool aff_add = AFF && a.in_add && a.add_n > 0;  // (the add applies with or without the ReLU)
 
   f32x16 acc[CBW][2];
 #pragma unroll
@@ -597,11 +598,11 @@ __device__ __forceinline__ void glds_tile(const GemmArgs &a, unsigned char *smem
         // fp16's range (65504) do not occur: scale = gamma * rstd <= gamma / sqrt(eps), shift and add are O(activations)
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb) bf[rb] = __builtin_elementwise_fma(bf[rb], sc, sh);
-        if (aff_relu) {  // deferred GroupNorm + ReLU + embedding add of the producing layer (module-level path)
+        if (aff_relu || aff_add) {  // deferred GroupNorm [+ ReLU] [+ embedding add] of the producing layer (module-level path)
           const f16x8 ad = *reinterpret_cast<const f16x8 *>(aff_w + 2 * a.k_pad + kc * BKT + piece * 8);
           const f16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-          for (int rb = 0; rb < 2; ++rb) bf[rb] = __builtin_elementwise_max(bf[rb], zero) + ad;
+          for (int rb = 0; rb < 2; ++rb) bf[rb] = (aff_relu ? __builtin_elementwise_max(bf[rb], zero) : bf[rb]) + ad;
         }
       }
 #pragma unroll
@@ -2461,7 +2462,12 @@ int run_gemm(const SlideOp &o, hipStream_t s) {
 #endif
   }
   // split mode, 16-row samples (and RAW-epilogue launches that ask for them): 64-row tiles
-  if (prec == SLIDE_PREC_SPLIT && npxl == 4 && cbw == 2 && o.i[9] != 3) return launch_gemm_split_small(a, s);
+  // (-8: the input affine's vectors do not fit the small kernel's 64 KB of LDS beside its ring -- k_pad >= 736 -- the 256-row
+  //  split tile below applies the affine per X row instead)
+  if (prec == SLIDE_PREC_SPLIT && npxl == 4 && cbw == 2 && o.i[9] != 3) {
+    const int st = launch_gemm_split_small(a, s);
+    if (st != -8) return st;
+  }
 #define CASE(P, L, C) if (prec == P && npxl == L && cbw == C) return launch_gemm<P, L, C>(a, s)
   CASE(SLIDE_PREC_F32, 4, 2); CASE(SLIDE_PREC_F32, 7, 2); CASE(SLIDE_PREC_F32, 8, 2);
   CASE(SLIDE_PREC_SPLIT, 4, 2); CASE(SLIDE_PREC_SPLIT, 7, 2); CASE(SLIDE_PREC_SPLIT, 8, 2);
