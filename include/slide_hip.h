@@ -17,6 +17,8 @@
  * Part 2 adds what the executed configs need from un-vendored pytorch3d 0.7.0 (knn_points /
  * knn_gather, call sites pointnet2_ops/pointnet2_utils.py:370,506-507).
  *
+ * Part 4 is the Chamfer / F1 metric (the reference's pointnet2/metrics_point_cloud/chamfer_and_f1.py, forward only).
+ *
  * Part 3 is the fused latent-DDPM denoiser engine (the reference runs these as ~80 torch module
  * launches per step: pointnet2/models/pointnet2_with_pcld_condition.py:286-489).
  */
@@ -84,6 +86,23 @@ SLIDE_API int slide_sample_farthest_points(int b, int n, int K, const float *poi
  * gathered element.  What FPS -> gather of the row-major module path and of (B,N,3) coordinates uses. */
 SLIDE_API int slide_gather_rows(int b, int n, int m, int c, const float *points, const int *idx, float *out,
                                 slide_stream_t stream);
+
+/* ------------------------------------------------------------------ Part 4: Chamfer / F1 metric */
+/* Bidirectional nearest neighbour (K = 1) of a batch of cloud pairs.  x (b,n1,sx) / y (b,n2,sy) f32 row-major, xyz = the first three
+ * floats of every point (sx, sy >= 3: a (B,N,C) tensor with features behind xyz is read in place); x_lengths / y_lengths (b) int64
+ * in [1, n] or NULL (= n).  -> d1 (b,n1) f32 squared L2 distance of each valid point of x to its nearest valid point of y, i1 (b,n1)
+ * int64 that point's index; d2 / i2 the other direction.  Bit-equal to slide_knn_points(K = 1) (ties -> lower index); slots beyond a
+ * cloud's length hold (0, 0).  Returns -2 for sx or sy < 3. */
+SLIDE_API int slide_chamfer_nn(int b, int n1, int n2, const float *x, int sx, const float *y, int sy, const int64_t *x_lengths,
+                               const int64_t *y_lengths, float *d1, int64_t *i1, float *d2, int64_t *i2, slide_stream_t stream);
+/* Per-cloud reductions of slide_chamfer_nn's output over the valid points, in a fixed order (a pair's results do not depend on its
+ * batch): out (b,2,5) f32, [pair][direction] = { sum d, sum sqrt d, count of d < threshold, sum term, sum sqrt term }.  term =
+ * the normal term between a point's features and its nearest neighbour's: mode 0 none (i1 / i2 / fx / fy may be NULL, the last two
+ * sums are 0), 1 mse sum_c (f - f_nn)^2, 2 cos 1 - |cosine_similarity(f, f_nn, eps = 1e-6)|.  fx (b,n1,sfx) / fy (b,n2,sfy): F
+ * channels per point at a row stride of sfx / sfy floats.  Returns -2 for an invalid mode / F / stride. */
+SLIDE_API int slide_chamfer_reduce(int b, int n1, int n2, const float *d1, const int64_t *i1, const float *d2, const int64_t *i2,
+                                   const int64_t *x_lengths, const int64_t *y_lengths, float threshold, int F, int mode,
+                                   const float *fx, int sfx, const float *fy, int sfy, float *out, slide_stream_t stream);
 
 /* ------------------------------------------------------------------ Part 3: denoiser engine */
 /* see slide_engine.h */

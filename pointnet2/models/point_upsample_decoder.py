@@ -58,21 +58,35 @@ class PointUpsampleDecoder(nn.Module):
         self.upsampling_setting = up
         self.fc_layer = HipConv1x1(query_dim + fm["out_dim"] + hp["in_fea_dim"] + 3, int(hp["out_dim"] * factor), ndim=1)
 
-    def propagate_feature(self, xyz, features, new_xyz, ts=None, label=None, sample_posterior=True):
-        """xyz (B,N1,3) with features (B,N1,C1) -> features at new_xyz (B,N2,3+in_fea): [extracted | mapped]"""
+    def propagate_feature(self, xyz, features, new_xyz, ts=None, label=None, sample_posterior=True, return_kl=False):
+        """xyz (B,N1,3) with features (B,N1,C1) -> features at new_xyz (B,N2,3+in_fea): [extracted | mapped], and None -- or, with
+        return_kl and apply_kl_regularization, the summed KL divergence of both posteriors from N(0, I), (B,) (reference :141-144)"""
         if self.decode_only:
             raise NotImplementedError("this level was built decode-only")
         out = self.feature_extractor(new_xyz, ts=ts, label=label)
         if isinstance(out, tuple):  # PointNet2Encoder returns (features, l_xyz, l_features)
             out = out[0]
+        kl = None
         if self.apply_kl_regularization:
+            if return_kl:
+                kl = self._kl(out)
             out = self._posterior(out, sample_posterior)
         mapped = self.feature_mapper(xyz, features.transpose(1, 2).contiguous(), new_xyz[:, :, 0:3].contiguous(), subset=False,
                                      record_neighbor_stats=False, pooling=None,
                                      features_at_new_xyz=out.transpose(1, 2).contiguous()).transpose(1, 2)
         if self.apply_kl_regularization:
+            if return_kl:
+                kl = kl + self._kl(mapped)
             mapped = self._posterior(mapped, sample_posterior)
-        return torch.cat([out, mapped], dim=2), None
+        return torch.cat([out, mapped], dim=2), kl
+
+    @staticmethod
+    def _kl(parameters):
+        """DiagonalGaussianDistribution.kl() against N(0, I) over the channel halves of (B,N,2C) -> (B,): 0.5 * the sum over channels
+        and points of mean^2 + var - 1 - logvar, logvar clamped to [-30, 20] (pointnet2/data_utils/distributions.py:4-32)"""
+        mean, logvar = torch.chunk(parameters, 2, dim=2)
+        logvar = torch.clamp(logvar, -30.0, 20.0)
+        return 0.5 * torch.sum(torch.pow(mean, 2) + torch.exp(logvar) - 1.0 - logvar, dim=[1, 2])
 
     @staticmethod
     def _posterior(parameters, sample):

@@ -226,3 +226,76 @@ def sample_farthest_points(points, lengths=None, K=50, random_start_point=False,
           "sample_farthest_points")
     idx = idx.long()
     return torch.gather(points, 1, idx.unsqueeze(-1).expand(-1, -1, points.shape[2])), idx
+
+
+# ------------------------------------------------------------------ Chamfer / F1 metric (include/slide_hip.h Part 4)
+def _pts3(t, name):
+    """(B,N,C >= 3) float32 CUDA tensor read in place (xyz = the first three channels) -> (contiguous tensor, point stride)"""
+    _need_gpu(t)
+    _chk_float(t, name)
+    if t.dim() != 3 or t.size(2) < 3:
+        raise RuntimeError("%s must be a (B, N, C >= 3) tensor" % name)
+    t = t.contiguous()
+    return t, t.size(2)
+
+
+def _lengths_ptr(lengths, dev):
+    if lengths is None:
+        return None, None
+    lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+    return lengths, ptr(lengths)
+
+
+def chamfer_nn(x, y, x_lengths=None, y_lengths=None):
+    """nearest neighbour (K = 1) in both directions: x (B,P1,C>=3), y (B,P2,C>=3) f32 (xyz = channels 0:3), lengths (B,) int64 in
+    [1, P] or None -> (d1 (B,P1) f32, i1 (B,P1) int64, d2 (B,P2), i2 (B,P2)): squared L2 distance to the nearest valid point of the
+    other cloud and its index; slots beyond a cloud's length (0, 0).  Bit-equal to knn_points(K=1) in each direction."""
+    x, sx = _pts3(x, "x")
+    y, sy = _pts3(y, "y")
+    _chk_cuda(y, "y")
+    B, P1, P2 = x.size(0), x.size(1), y.size(1)
+    if y.size(0) != B:
+        raise RuntimeError("x and y must have the same batch size")
+    d1 = torch.empty((B, P1), device=x.device, dtype=torch.float32)
+    i1 = torch.empty((B, P1), device=x.device, dtype=torch.int64)
+    d2 = torch.empty((B, P2), device=x.device, dtype=torch.float32)
+    i2 = torch.empty((B, P2), device=x.device, dtype=torch.int64)
+    lx, lxp = _lengths_ptr(x_lengths, x.device)
+    ly, lyp = _lengths_ptr(y_lengths, x.device)
+    check(lib().slide_chamfer_nn(B, P1, P2, ptr(x), sx, ptr(y), sy, lxp, lyp, ptr(d1), ptr(i1), ptr(d2), ptr(i2), stream_of()),
+          "chamfer_nn")
+    return d1, i1, d2, i2
+
+
+CHAMFER_TERM = {None: 0, "mse": 1, "cos": 2}
+
+
+def chamfer_reduce(d1, i1, d2, i2, x_lengths=None, y_lengths=None, threshold=1e-4, fx=None, fy=None, term=None):
+    """per-cloud sums of chamfer_nn's output over the valid points, in a fixed order -> (B, 2, 5) f32:
+    [pair][direction] = (sum d, sum sqrt d, count d < threshold, sum term, sum sqrt term).  fx (B,P1,F) / fy (B,P2,F) per-point
+    features (any row stride: a channel slice of a (B,N,C) tensor is read in place) and term in {"mse", "cos"}, or both None."""
+    mode = CHAMFER_TERM[term]
+    B, P1 = d1.shape
+    P2 = d2.shape[1]
+    for t, n in ((d1, "d1"), (d2, "d2")):
+        _chk_contig(t, n); _chk_float(t, n); _need_gpu(t)
+    F = sfx = sfy = 0
+    pfx = pfy = pi1 = pi2 = None
+    if mode:
+        i1 = i1.contiguous(); i2 = i2.contiguous()
+        pi1, pi2 = ptr(i1), ptr(i2)
+        F = fx.size(2)
+        if fy.size(2) != F:
+            raise RuntimeError("fx and fy must have the same number of channels")
+        for t, n in ((fx, "fx"), (fy, "fy")):
+            _chk_float(t, n); _need_gpu(t)
+            if t.stride(2) != 1 or t.stride(0) != t.size(1) * t.stride(1):
+                raise RuntimeError("%s must be a channel slice of a contiguous (B, N, C) tensor" % n)
+        sfx, sfy = fx.stride(1), fy.stride(1)
+        pfx, pfy = ptr(fx), ptr(fy)
+    lx, lxp = _lengths_ptr(x_lengths, d1.device)
+    ly, lyp = _lengths_ptr(y_lengths, d1.device)
+    out = torch.empty((B, 2, 5), device=d1.device, dtype=torch.float32)
+    check(lib().slide_chamfer_reduce(B, P1, P2, ptr(d1), pi1, ptr(d2), pi2, lxp, lyp, ctypes.c_float(threshold), F, mode,
+                                     pfx, sfx, pfy, sfy, ptr(out), stream_of()), "chamfer_reduce")
+    return out

@@ -10,6 +10,9 @@ copied) on seeded inputs and records inputs + outputs as small fixtures:
   golden_denoiser_condition.npz   the same forward WITH a condition cloud (local feature transfer, global feature, both; retained features)
   golden_blocks.npz               stand-alone reference modules (QueryAndGroup, group_knn, Mlp_plus_t_emb,
                                   AttentionModule, PointnetSAModule w/ FPS, PointnetFPModule (three_nn path))
+  golden_chamfer.npz              metrics_point_cloud/chamfer_and_f1.py: chamfer_distance (every reduction pair, normals, weights,
+                                  lengths, ties), calc_cd, fscore
+  golden_ae_forward.npz           PointAutoencoder.forward (evaluation: every decoder level + loss_list)
   golden_ops.npz                  op-level adversarial cases (computed by the C oracle -- the reference has
                                   no CPU path for `_ext`; the oracle itself is pinned by the files above)
 Weights are NOT stored: slide_amd.synth.synth_state_dict(spec) regenerates them from the names.
@@ -729,6 +732,111 @@ def gen_ops(out):
     print("ops done")
 
 
+REDUCTIONS = [(None, None), ("mean", None), ("mean", "mean"), ("mean", "sum"), ("sum", None), ("sum", "mean"), ("sum", "sum")]
+
+
+def chamfer_cases():
+    """the seeded inputs of golden_chamfer.npz: (name, x, y, x_lengths, y_lengths, x_normals, y_normals, weights)"""
+    rs = np.random.RandomState(71)
+    cases = []
+    # coordinates on a 0.25 grid: exact duplicate points and exactly equidistant neighbours (ties -> the lower index)
+    x = (rs.randint(0, 4, (3, 37, 3)) * 0.25).astype(np.float32)
+    y = (rs.randint(0, 4, (3, 53, 3)) * 0.25).astype(np.float32)
+    y[:, 40:50] = y[:, 0:10]
+    cases.append(("grid", x, y, np.array([37, 20, 5], np.int64), np.array([53, 53, 1], np.int64),
+                  rs.standard_normal((3, 37, 3)).astype(np.float32), rs.standard_normal((3, 53, 3)).astype(np.float32),
+                  np.array([0.5, 2.0, 1.0], np.float32)))
+    # random clouds, P1 != P2, homogeneous lengths
+    cases.append(("rand", rs.standard_normal((2, 64, 3)).astype(np.float32), rs.standard_normal((2, 48, 3)).astype(np.float32),
+                  None, None, rs.standard_normal((2, 64, 3)).astype(np.float32), rs.standard_normal((2, 48, 3)).astype(np.float32),
+                  np.array([1.5, 0.25], np.float32)))
+    return cases
+
+
+def gen_chamfer(out):
+    """the reference's metrics_point_cloud/chamfer_and_f1.py (imported; knn_points = the oracle's K = 1 through the shim):
+    chamfer_distance over every reduction pair x normals (none / cos / mse) x weights (none / positive / all zero) on two cases
+    (0.25-grid clouds with duplicates, ties and heterogeneous lengths; random clouds with P1 != P2), the per-point K = 1 neighbours
+    of both directions, calc_cd with and without features, fscore (a case with no point under the threshold: NaN -> 0)."""
+    import metrics_point_cloud.chamfer_and_f1 as C
+    from oracle import ops as O
+    res = {}
+    t = torch.from_numpy
+    with torch.no_grad():
+        for name, x, y, lx, ly, nx, ny, w in chamfer_cases():
+            res[name + "_x"], res[name + "_y"] = x, y
+            res[name + "_nx"], res[name + "_ny"], res[name + "_w"] = nx, ny, w
+            if lx is not None:
+                res[name + "_lx"], res[name + "_ly"] = lx, ly
+            d, i = O.knn_points(x, y, 1, ly)
+            res[name + "_knn_d1"], res[name + "_knn_i1"] = d[..., 0], i[..., 0]
+            d, i = O.knn_points(y, x, 1, lx)
+            res[name + "_knn_d2"], res[name + "_knn_i2"] = d[..., 0], i[..., 0]
+            tl = (lambda a: None if a is None else t(a))
+            for nt in ("none", "cos", "mse"):
+                for wt in ("none", "w", "zero"):
+                    for pr, br in REDUCTIONS:
+                        r = C.chamfer_distance(t(x), t(y), x_lengths=tl(lx), y_lengths=tl(ly),
+                                               x_normals=None if nt == "none" else t(nx), y_normals=None if nt == "none" else t(ny),
+                                               normal_loss_type="cos" if nt == "none" else nt,
+                                               weights=None if wt == "none" else (t(w) if wt == "w" else t(np.zeros_like(w))),
+                                               batch_reduction=br, point_reduction=pr)
+                        key = "%s_cd_%s_%s_%s_%s" % (name, nt, wt, pr, br)
+                        for k, v in enumerate(r):
+                            res["%s_%d" % (key, k)] = v.numpy()
+        rs = np.random.RandomState(72)
+        for C_, tag in ((6, "feat"), (3, "xyz")):
+            gt = (0.3 * rs.standard_normal((3, 96, C_))).astype(np.float32)
+            o = (gt[:, :80] + 0.02 * rs.standard_normal((3, 80, C_))).astype(np.float32)
+            o[2] += 5.0  # the third pair is far apart: no point under the threshold, F1 = 0 / 0 -> 0
+            res["calc_%s_out" % tag], res["calc_%s_gt" % tag] = o, gt
+            for nt in ("cos", "mse"):
+                r = C.calc_cd(t(o), t(gt), calc_f1=True, f1_threshold=1e-3, normal_loss_type=nt)
+                for k, v in r.items():
+                    res["calc_%s_%s_%s" % (tag, nt, k)] = v.numpy()
+        d1 = np.abs(rs.standard_normal((4, 50))).astype(np.float32) * 0.01
+        d2 = np.abs(rs.standard_normal((4, 70))).astype(np.float32) * 0.01
+        d1[3] += 1.0
+        d2[3] += 1.0
+        res["fscore_d1"], res["fscore_d2"] = d1, d2
+        for k, v in zip(("f", "p1", "p2"), C.fscore(t(d1), t(d2), threshold=0.005)):
+            res["fscore_" + k] = v.numpy()
+    np.savez_compressed(os.path.join(out, "golden_chamfer.npz"), **res)
+    print("chamfer", len(res), "arrays")
+
+
+def gen_ae_forward(out):
+    """PointAutoencoder.forward of the reference (airplane AE config, feature_weight [0, 0, 0.1], KL weight 1e-5, synthetic weights as
+    gen_encode builds them) on golden_encode.npz's clouds and key points, posterior mode (sample_posterior=False), loss_type cd_p;
+    every farthest point sampling starts at index 0 (shim).  Records every level of l_xyz_decoder and every key of loss_list."""
+    from data_utils.json_reader import read_json_file, autoencoder_read_config
+    from models.autoencoder import PointAutoencoder
+    d = CFG + "autoencoder_configs/"
+    cfg = read_json_file(d + "config_autoencoder_s3_kl_1e-5_16_keypoints_latent_dim_16_32_normal_weight_0_0_0.1_with_augm_kp_noise_0.04_airplane.json")
+    pc_cfg = cfg["pointnet_config"]
+    enc, decs = autoencoder_read_config(d, cfg)
+    ae = PointAutoencoder(enc, decs, apply_kl_regularization=pc_cfg["apply_kl_regularization"], kl_weight=pc_cfg["kl_weight"],
+                          feature_weight=pc_cfg["feature_weight"])
+    spec_all = [(k, tuple(v.shape)) for k, v in ae.state_dict().items()]
+    vals = synth_state_dict([("ae." + n, s) for n, s in spec_all])
+    ae.load_state_dict({n: torch.from_numpy(vals["ae." + n]) for n, _ in spec_all})
+    ae.eval()
+    g = np.load(os.path.join(REPO, "tests", "golden", "golden_encode.npz"))
+    pc, kp, label = g["pointcloud"], g["keypoint"], g["label"]
+    with torch.no_grad():
+        l_xyz, loss_list = ae(torch.from_numpy(pc), torch.from_numpy(kp), ts=None, label=torch.from_numpy(label), loss_type="cd_p",
+                              sample_posterior=False)
+    res = {"feature_weight": np.array(pc_cfg["feature_weight"], np.float32), "kl_weight": np.float32(pc_cfg["kl_weight"]),
+           "levels": np.int64(len(l_xyz))}
+    for i, v in enumerate(l_xyz):
+        res["level%d" % i] = v.numpy()
+    for i, dct in enumerate(loss_list):
+        for k, v in dct.items():
+            res["loss%d_%s" % (i, k)] = v.numpy().astype(np.float32)
+    np.savez_compressed(os.path.join(out, "golden_ae_forward.npz"), **res)
+    print("ae forward", [tuple(v.shape) for v in l_xyz], {k: v.tolist() for k, v in loss_list[-1].items()})
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
@@ -736,7 +844,8 @@ if __name__ == "__main__":
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     torch.manual_seed(0)
-    want = set(a.only.split(",")) if a.only else {"ops", "blocks", "pos", "feat", "variants", "condition", "switches", "resample", "sched", "train", "decode", "encode"}
+    want = set(a.only.split(",")) if a.only else {"ops", "blocks", "pos", "feat", "variants", "condition", "switches", "resample", "sched", "train", "decode", "encode", "chamfer",
+                                                         "aeforward"}
     if "ops" in want:
         gen_ops(a.out)
     if "blocks" in want:
@@ -768,3 +877,7 @@ if __name__ == "__main__":
         gen_decode(a.out)
     if "encode" in want:
         gen_encode(a.out)
+    if "chamfer" in want:
+        gen_chamfer(a.out)
+    if "aeforward" in want:
+        gen_ae_forward(a.out)
