@@ -416,7 +416,10 @@ def test_row_major_modules_against_the_oracle(gpu_device, monkeypatch, prec):
     from oracle import denoiser_np as O
     from pointnet2_ops import pointnet2_modules as PM
     monkeypatch.setenv("SLIDE_MODULE_PREC", prec)
-    tol = dict(atol=3e-4, rtol=2e-4) if prec == "fp32" else dict(atol=4e-2, rtol=4e-2)
+    # fp16 rows: measured worst |got - oracle| / (1 + |oracle|) over the four module programs 7.3e-3 (printed below); the tolerance is
+    # twice that (the margin is for another seed's draw).  It was 4e-2 until the row ops had references of their own
+    # (tests/test_hip_rows_arith.py).
+    tol = dict(atol=3e-4, rtol=2e-4) if prec == "fp32" else dict(atol=1.46e-2, rtol=1.46e-2)
     d = gpu_device
     gen = torch.Generator().manual_seed(5)
     B, N, C = 3, 200, 13
@@ -426,7 +429,11 @@ def test_row_major_modules_against_the_oracle(gpu_device, monkeypatch, prec):
     npy = lambda t: t.detach().cpu().numpy()
     att = {"use_attention_module": True, "attention_bn": True, "transform_grouped_feat_out": True, "last_activation": True}
 
+    worst = [0.0]
+
     def close(a, b):
+        # allclose with atol == rtol == t asks |a - b| <= t (1 + |b|): the measured figure is the largest |a - b| / (1 + |b|)
+        worst[0] = max(worst[0], float((np.abs(a - b) / (1 + np.abs(b))).max()))
         assert a.shape == b.shape and np.allclose(a, b, **tol), float(np.abs(a - b).max())
 
     # two scales (5 and 48 neighbours), t and class embeddings, res_connect through a convolution
@@ -470,6 +477,7 @@ def test_row_major_modules_against_the_oracle(gpu_device, monkeypatch, prec):
     out = fm(xyz.to(d), feats.to(d), keypts.to(d), subset=False, record_neighbor_stats=True, features_at_new_xyz=qf.to(d))
     close(npy(out), O.feature_map_module(npy(xyz), npy(feats), npy(keypts), npy(qf), _sd(fm, "fm"), "fm", 12))
     assert float(fm.mapper.neighbor_stats[0]) == 12.0
+    print("row-major modules %s: worst |got - oracle| / (1 + |oracle|) %.3e (tolerance %.1e)" % (prec, worst[0], tol["atol"]))
 
 
 def test_general_module_programs_against_torch(gpu_device):
