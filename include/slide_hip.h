@@ -103,6 +103,15 @@ SLIDE_API int slide_chamfer_nn(int b, int n1, int n2, const float *x, int sx, co
 SLIDE_API int slide_chamfer_reduce(int b, int n1, int n2, const float *d1, const int64_t *i1, const float *d2, const int64_t *i2,
                                    const int64_t *x_lengths, const int64_t *y_lengths, float threshold, int F, int mode,
                                    const float *fx, int sfx, const float *fy, int sfy, float *out, slide_stream_t stream);
+/* All-pairs Chamfer sums of two SETS of fixed-size clouds, one launch: x (m,p,sx) / y (n,q,sy) f32 row-major, xyz = the first three
+ * floats of every point (sx, sy >= 3) -> out (m,n,2,2) f32, out[i][j][0] = { sum, sum of square roots } over the points of x[i] of
+ * the squared L2 distance to the nearest point of y[j], out[i][j][1] the same over the points of y[j] towards x[i].  Every entry is
+ * bit-equal to columns 0 and 1 of slide_chamfer_reduce(slide_chamfer_nn(x[i], y[j])) and does not depend on m, n, the pair's
+ * position or `symmetric`.  symmetric = 1: y is x (m == n, p == q); the upper triangle and the diagonal are computed, the lower
+ * triangle is their mirror out[j][i][d] = out[i][j][1 - d].  Returns -2 for sx or sy < 3, for symmetric with m != n or p != q and
+ * for more than 2^31 - 1 workgroups (8 * ceil(n / 8) * m); 0 without a launch when m, n, p or q is 0. */
+SLIDE_API int slide_chamfer_pairwise(int m, int n, int p, int q, const float *x, int sx, const float *y, int sy, int symmetric,
+                                     float *out, slide_stream_t stream);
 
 /* ------------------------------------------------------------------ Part 3: denoiser engine */
 /* see slide_engine.h */

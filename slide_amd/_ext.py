@@ -299,3 +299,25 @@ def chamfer_reduce(d1, i1, d2, i2, x_lengths=None, y_lengths=None, threshold=1e-
     check(lib().slide_chamfer_reduce(B, P1, P2, ptr(d1), pi1, ptr(d2), pi2, lxp, lyp, ctypes.c_float(threshold), F, mode,
                                      pfx, sfx, pfy, sfy, ptr(out), stream_of()), "chamfer_reduce")
     return out
+
+
+def chamfer_pairwise(x, y=None):
+    """all-pairs Chamfer sums of two sets of fixed-size clouds in one launch: x (M,P,C>=3), y (N,Q,C>=3) f32 CUDA tensors (xyz =
+    channels 0:3, read in place) -> (M,N,2,2) f32, [i][j][direction] = (sum d, sum sqrt d): direction 0 over the points of x[i]
+    towards y[j], direction 1 over the points of y[j] towards x[i].  y=None: the symmetric form (y is x; the upper triangle is
+    computed and mirrored).  Every entry is bit-equal to chamfer_reduce(*chamfer_nn(x[i:i+1], y[j:j+1]))[0, :, :2]."""
+    x, sx = _pts3(x, "x")
+    symmetric = y is None
+    if symmetric:
+        y, sy = x, sx
+    else:
+        y, sy = _pts3(y, "y")
+        if y.device != x.device:
+            raise RuntimeError("x and y must be on the same device")
+    M, P, N, Q = x.size(0), x.size(1), y.size(0), y.size(1)
+    if M and N and not (P and Q):
+        raise RuntimeError("chamfer_pairwise: clouds must hold at least one point")
+    out = torch.empty((M, N, 2, 2), device=x.device, dtype=torch.float32)
+    check(lib().slide_chamfer_pairwise(M, N, P, Q, ptr(x), sx, ptr(y), sy, int(symmetric), ptr(out), stream_of()),
+          "chamfer_pairwise")
+    return out
