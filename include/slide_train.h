@@ -54,6 +54,21 @@ SLIDE_API int slide_concat_qk_bwd(long long pts, int K, int C1, int ldq, int C2,
 SLIDE_API int slide_attn_rows_bwd(long long pts, int K, int C, int lds, int ldv, int ldo, const float *s, const float *v,
                                   const int *counts, const float *dout, float *ds, float *dv, slide_stream_t stream);
 
+/* Backward of the fused Chamfer path (slide_hip.h Part 4: slide_chamfer_nn + slide_chamfer_reduce without lengths; feature term
+ * `mse`, or none with f = 0) -- the reference's autoencoder loss, pointnet2/metrics_point_cloud/chamfer_and_f1.py:242-265.
+ * x [b][n1][*], y [b][n2][*]: f32 rows of sx / sy >= 3 + f floats, xyz then f <= 16 feature channels; (d1, i1), (d2, i2): what
+ * slide_chamfer_nn returned for (x, y); dred [b][2][5]: the gradient w.r.t. slide_chamfer_reduce's output (column 2, the F1 count,
+ * is ignored).  Writes the dense gradients dx [b][n1][3 + f] and dy [b][n2][3 + f] in full; either may be NULL (not computed).
+ * A point p of direction dir with neighbour q, squared distance d and feature term t = sum_c (fp_c - fq_c)^2 gives
+ *   v = 2 (dred[dir][0] + dred[dir][1] / (2 sqrt d)) (p_xyz - q_xyz),  w = 2 (dred[dir][3] + dred[dir][4] / (2 sqrt t)) (fp - fq),
+ * +v, +w to p and -v, -w to q.  CONVENTION: where d == 0 (t == 0) the square root's part is 0 -- the subgradient 0, where torch's
+ * autograd yields NaN -- so the gradients are finite for all finite inputs.  Deterministic: every element is stored once, its
+ * value the own-direction term and then the incoming terms in ascending source index (no atomics); a cloud's gradient does not
+ * depend on its position in the batch.  b == 0: 0 without a launch; bad arguments (f, strides, NULL inputs): -2. */
+SLIDE_API int slide_chamfer_cd_bwd(int b, int n1, int n2, int f, const float *x, int sx, const float *y, int sy, const float *d1,
+                                   const int64_t *i1, const float *d2, const int64_t *i2, const float *dred, float *dx, float *dy,
+                                   slide_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

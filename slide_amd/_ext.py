@@ -301,6 +301,32 @@ def chamfer_reduce(d1, i1, d2, i2, x_lengths=None, y_lengths=None, threshold=1e-
     return out
 
 
+def chamfer_cd_bwd(x, y, d1, i1, d2, i2, dred, need_dx=True, need_dy=True):
+    """backward of chamfer_reduce(*chamfer_nn(x, y), fx=x[:, :, 3:], fy=y[:, :, 3:], term="mse") (term None when C = 3) in one launch
+    (include/slide_train.h slide_chamfer_cd_bwd): x (B,P1,C), y (B,P2,C) f32, C = 3 + F with F <= 16, (d1, i1, d2, i2) chamfer_nn's
+    output for them, dred (B,2,5) the gradient of the reduced sums -> (dx (B,P1,C), dy (B,P2,C)); None for one that is not needed.
+    Where a distance (or a feature term) is 0 its square root contributes the subgradient 0 (torch's autograd: NaN).  Deterministic:
+    no atomics, every element stored once in a fixed summation order."""
+    x, sx = _pts3(x, "x")
+    y, sy = _pts3(y, "y")
+    B, P1, P2, C = x.size(0), x.size(1), y.size(1), x.size(2)
+    if y.size(0) != B or y.size(2) != C:
+        raise RuntimeError("x and y must have the same batch size and channel count")
+    if C - 3 > 16:
+        raise RuntimeError("chamfer_cd_bwd supports at most 16 feature channels")
+    for t, n, shape, dt in ((d1, "d1", (B, P1), torch.float32), (d2, "d2", (B, P2), torch.float32), (i1, "i1", (B, P1), torch.int64),
+                            (i2, "i2", (B, P2), torch.int64), (dred, "dred", (B, 2, 5), torch.float32)):
+        _chk_cuda(t, n); _chk_contig(t, n)
+        if t.dtype != dt or tuple(t.shape) != shape:
+            raise RuntimeError("%s must be a %s tensor of shape %s" % (n, dt, shape))
+    dx = torch.empty((B, P1, C), device=x.device, dtype=torch.float32) if need_dx else None
+    dy = torch.empty((B, P2, C), device=x.device, dtype=torch.float32) if need_dy else None
+    check(lib().slide_chamfer_cd_bwd(B, P1, P2, C - 3, ptr(x), sx, ptr(y), sy, ptr(d1), ptr(i1), ptr(d2), ptr(i2), ptr(dred),
+                                     None if dx is None else ptr(dx), None if dy is None else ptr(dy), stream_of()),
+          "chamfer_cd_bwd")
+    return dx, dy
+
+
 def chamfer_pairwise(x, y=None):
     """all-pairs Chamfer sums of two sets of fixed-size clouds in one launch: x (M,P,C>=3), y (N,Q,C>=3) f32 CUDA tensors (xyz =
     channels 0:3, read in place) -> (M,N,2,2) f32, [i][j][direction] = (sum d, sum sqrt d): direction 0 over the points of x[i]

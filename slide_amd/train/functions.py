@@ -8,6 +8,9 @@ import weakref
 import numpy as np
 import torch
 
+from torch.autograd.function import once_differentiable
+
+from .. import _ext
 from .._lib import check, lib
 from ..engine import EPI_RAW, OP_GEMM, SlideEpi, make_op, ru
 from ..rows import (GN_POST_RELU, GN_PRE_RELU, GROUP_ABS, GROUP_CENTER, GROUP_FP, OP_ROWS_ATTN, OP_ROWS_CONCAT_QK, OP_ROWS_GN,
@@ -289,6 +292,53 @@ class AttendRows(torch.autograd.Function):
         check(lib().slide_attn_rows_bwd(ctypes.c_longlong(pts), K, C, scores.shape[1], values.shape[1], ldo, _p(scores), _p(values), None,
                                         _p(dout), _p(ds), _p(dv), _stream()), "slide_attn_rows_bwd")
         return ds, dv, None, None
+
+
+class ChamferCD(torch.autograd.Function):
+    """per-cloud Chamfer sums of (output, gt) -> red (B, 2, 5), direction 0 = gt -> output: chamfer_nn + chamfer_reduce exactly as
+    metrics_point_cloud.chamfer_and_f1.calc_cd_reduced calls them (feature term `mse` when C > 3), bit-equal to it.  Backward: one
+    launch of csrc/chamfer_bwd.hip (include/slide_train.h slide_chamfer_cd_bwd) on the saved neighbours; no double backward.  Where a
+    distance or a feature term is 0 its square root contributes the subgradient 0 (torch's autograd: NaN)."""
+
+    @staticmethod
+    def forward(ctx, output, gt, f1_threshold):
+        gt = gt.detach().contiguous()
+        output = output.detach().contiguous()
+        d1, i1, d2, i2 = _ext.chamfer_nn(gt, output)
+        if gt.shape[2] > 3:
+            red = _ext.chamfer_reduce(d1, i1, d2, i2, threshold=f1_threshold, fx=gt[:, :, 3:], fy=output[:, :, 3:], term="mse")
+        else:
+            red = _ext.chamfer_reduce(d1, None, d2, None, threshold=f1_threshold)
+        ctx.save_for_backward(gt, output, d1, i1, d2, i2)
+        return red
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dred):
+        gt, output, d1, i1, d2, i2 = ctx.saved_tensors
+        dgt, dout = _ext.chamfer_cd_bwd(gt, output, d1, i1, d2, i2, dred.contiguous(), need_dx=ctx.needs_input_grad[1],
+                                        need_dy=ctx.needs_input_grad[0])
+        return dout, dgt, None
+
+
+def chamfer_cd(output, gt, f1_threshold=1e-4):
+    """differentiable counterpart of calc_cd_reduced(output, gt, f1_threshold, 'mse')[0]: output (B, P_out, C), gt (B, P_gt, C) fp32
+    CUDA tensors, C = 3 + F (F <= 16 feature channels) -> red (B, 2, 5) = [pair][direction] (sum d, sum sqrt d, count d < threshold,
+    sum t, sum sqrt t), direction 0 over gt's points; differentiable in both clouds (the count has no gradient)."""
+    if not (torch.is_tensor(output) and torch.is_tensor(gt)) or output.ndim != 3 or gt.ndim != 3:
+        raise ValueError("Expected points to be of shape (N, P, D)")
+    if output.shape[0] != gt.shape[0] or output.shape[2] != gt.shape[2]:
+        raise ValueError("y does not have the correct shape.")
+    if gt.shape[1] < 1 or output.shape[1] < 1 or gt.shape[2] < 3:
+        raise ValueError("point clouds must hold at least one point of at least three channels")
+    if gt.shape[2] > 3 + 16:
+        raise ValueError("at most 16 feature channels are supported")
+    for t in (output, gt):
+        if not t.is_cuda:
+            raise RuntimeError("CPU not supported: the Chamfer loss launches HIP kernels")
+        if t.dtype != torch.float32:
+            raise RuntimeError("the Chamfer loss takes float32 tensors")
+    return ChamferCD.apply(output, gt, float(f1_threshold))
 
 
 def conv_rows(x, weight, bias=None):

@@ -1,6 +1,7 @@
 """Training losses of the two latent DDPMs, restated from the reference (forward = slide_amd.train.denoiser.TrainableDenoiser or any
 callable net(x_t, ts, label) -> eps prediction).  Random timesteps and noise are drawn here unless they are passed in (the parity
-tests inject the reference's)."""
+tests inject the reference's); and the autoencoder's Chamfer losses (calc_cd_loss, autoencoder_losses) on the differentiable
+Chamfer sums of functions.ChamferCD."""
 import numpy as np
 import torch
 
@@ -59,3 +60,67 @@ def latent_training_loss(net, x, keypoint, label, standard_diffusion_config, ste
     mse = (out - z) ** 2
     loss = w_kp * mse[:, :, :kd].sum(dim=2) + w_f * mse[:, :, kd:].mean(dim=2)
     return loss.mean(dim=1)
+
+
+def calc_cd_loss(output, gt, calc_f1=False, f1_threshold=1e-4, normal_loss_type='mse'):
+    """differentiable calc_cd (pointnet2/metrics_point_cloud/chamfer_and_f1.py:242-265) of output vs gt (B, N, C >= 3; xyz = channels
+    0:3, features behind them): the reference's dict -- cd_p, cd_t, with features cd_feature_p / cd_feature_t of the `mse` term, with
+    calc_f1 the (non-differentiable) F-score -- each (B,), values bit-equal to metrics_point_cloud.chamfer_and_f1.calc_cd, gradients
+    into both clouds through functions.ChamferCD (one backward launch).  Where two points coincide (or their features do) the square
+    root in cd_p / cd_feature_p contributes the subgradient 0; the reference's autograd yields NaN there.
+    normal_loss_type='cos' has no backward kernel: NotImplementedError."""
+    from .functions import chamfer_cd
+    if normal_loss_type != 'mse':
+        if normal_loss_type == 'cos':
+            raise NotImplementedError("calc_cd_loss: the `cos` feature term has no backward kernel (normal_loss_type='mse' only)")
+        raise ValueError("normal_loss_type must be 'mse' or 'cos'")
+    red = chamfer_cd(output, gt, f1_threshold)
+    n_gt, n_out = gt.shape[1], output.shape[1]
+    result = {}
+    result['cd_p'] = (red[:, 0, 1] / n_gt + red[:, 1, 1] / n_out) / 2
+    result['cd_t'] = red[:, 0, 0] / n_gt + red[:, 1, 0] / n_out
+    if gt.shape[2] > 3:
+        result['cd_feature_p'] = (red[:, 0, 4] / n_gt + red[:, 1, 4] / n_out) / 2
+        result['cd_feature_t'] = red[:, 0, 3] / n_gt + red[:, 1, 3] / n_out
+    if calc_f1:
+        cnt = red.detach()
+        p1 = cnt[:, 0, 2] / n_gt
+        p2 = cnt[:, 1, 2] / n_out
+        f = 2 * p1 * p2 / (p1 + p2)
+        result['f1'] = torch.where(torch.isnan(f), torch.zeros_like(f), f)
+    return result
+
+
+def autoencoder_losses(l_xyz_decoder, pointcloud, feature_weight, loss_type='cd_p', kl_loss=None, kl_weight=0,
+                       apply_kl_regularization=False, fps_start_idx=None):
+    """the loss loop of PointAutoencoder.forward (pointnet2/models/autoencoder.py:60-87) on given decoder levels: l_xyz_decoder =
+    [key points, level 1, ...]; every level i >= 1 is scored against `pointcloud` (B, N, 3 | 6) farthest-point-sampled to the level's
+    size (not differentiated; fps_start_idx (B,) int pins the start, None draws it) with calc_cd_loss(..., calc_f1=True,
+    normal_loss_type='mse'); training_loss = cd_p | cd_t + feature_weight[i-1] x the matching feature term (feature_weight None: 0)
+    and, with KL regularisation and kl_weight > 0, + kl_weight x kl_loss at the last level only.  -> loss_list of the reference's
+    dicts; gradients flow into the levels and kl_loss."""
+    from .. import _ext
+    assert pointcloud.shape[2] in [3, 6]
+    if loss_type not in ('cd_p', 'cd_t'):
+        raise Exception('loss type %s is not supported yet' % loss_type)
+    has_feature = pointcloud.shape[2] > 3
+    loss_list = []
+    for i in range(1, len(l_xyz_decoder)):
+        uvw = l_xyz_decoder[i]
+        with torch.no_grad():
+            downsampled, _ = _ext.sample_farthest_points(pointcloud.detach().contiguous(), K=uvw.shape[1],
+                                                         random_start_point=fps_start_idx is None, start_idx=fps_start_idx)
+        loss_dict = calc_cd_loss(uvw, downsampled, calc_f1=True, f1_threshold=0.0001, normal_loss_type='mse')
+        w = 0 if feature_weight is None else feature_weight[i - 1]
+        loss = loss_dict[loss_type]
+        if has_feature:
+            loss = loss + loss_dict['cd_feature_' + loss_type[-1]] * w
+        if apply_kl_regularization and kl_weight > 0:
+            if i == len(l_xyz_decoder) - 1:  # the KL term is added once, at the last level
+                loss_dict['kl_loss'] = kl_loss
+                loss = loss + kl_weight * loss_dict['kl_loss']
+            else:
+                loss_dict['kl_loss'] = torch.zeros_like(loss)
+        loss_dict['training_loss'] = loss
+        loss_list.append(loss_dict)
+    return loss_list
