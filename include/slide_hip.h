@@ -113,6 +113,19 @@ SLIDE_API int slide_chamfer_reduce(int b, int n1, int n2, const float *d1, const
 SLIDE_API int slide_chamfer_pairwise(int m, int n, int p, int q, const float *x, int sx, const float *y, int sy, int symmetric,
                                      float *out, slide_stream_t stream);
 
+/* Occupancy counters of S clouds of P points on an R^3 lattice (the JSD metric's grid_counters / grid_bernoulli_rvars), one launch.
+ * pts (s,p,sp) f32 row-major, xyz = the first three floats of a point (sp >= 3); axis (r) f32, the strictly ascending cell-centre
+ * coordinates of one axis (cell (i,j,k) = (axis[i], axis[j], axis[k]), flat index (i r + j) r + k); rowmask (r*r) uint32, bit k of
+ * word i r + j set when cell (i,j,k) is admissible; 2 <= r <= 32.  Every point goes to the admissible cell with the smallest fp32
+ * squared distance fmaf(dz, dz, fmaf(dy, dy, dx * dx)), exact ties to the lowest flat index (the two-step rule is written out in
+ * csrc/occupancy_grid.hip).  ACCUMULATED into (the caller zero-fills): counts (r^3) int32 += points per cell, clouds (r^3) int32 +=
+ * clouds with at least one point in the cell, flag (1) int32 |= 1 when a point with a non-finite coordinate was left out, |= 2
+ * when no cell is admissible.  cells (s,p) int32 or NULL: every point's cell (-1 for a point left out).  Integer atomics only: the
+ * result does not depend on the order of points or clouds.  Returns -2 for sp < 3, r outside [2, 32], s * p > 2^31 - 1 or a NULL
+ * pointer other than cells; 0 without a launch when s or p is 0. */
+SLIDE_API int slide_occupancy_grid(int s, int p, const float *pts, int sp, int r, const float *axis, const uint32_t *rowmask,
+                                   int *counts, int *clouds, int *cells, int *flag, slide_stream_t stream);
+
 /* ------------------------------------------------------------------ Part 3: denoiser engine */
 /* see slide_engine.h */
 SLIDE_API const char *slide_hip_version(void);

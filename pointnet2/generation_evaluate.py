@@ -4,9 +4,12 @@
 Both sets are npz files with the clouds under one key ((S, N, C >= 3), xyz first) -- the layout the generation CLIs write and
 load_evaluate.py reads.  With --normalize both sets are normalised by load_evaluate.normalize_point_cloud (per shape, one standard
 deviation per axis by default) before scoring.  Prints the six numbers and the wall time; --save writes them as JSON.
+With --jsd the result also carries JSD, the Jensen-Shannon divergence between the two sets' occupancy distributions on a
+--jsd_resolution^3 grid clipped to the unit sphere (generation_metrics.jsd_between_point_cloud_sets), computed after --normalize.
 
 usage:  python pointnet2/generation_evaluate.py --samples generated.npz --ref reference.npz [--key points] [--normalize]
-            [--normalize_std_per_axis 0|1] [--normalize_per_shape 0|1] [--device cuda:0] [--save metrics.json]
+            [--normalize_std_per_axis 0|1] [--normalize_per_shape 0|1] [--jsd [--jsd_resolution 28]] [--device cuda:0]
+            [--save metrics.json]
 """
 import argparse
 import json
@@ -31,20 +34,26 @@ def build_parser():
     p.add_argument('--normalize_std_per_axis', type=int, default=1, choices=(0, 1), help="one std per axis (1) or one scale (0)")
     p.add_argument('--normalize_per_shape', type=int, default=1, choices=(0, 1),
                    help="statistics per shape (1) or over the whole set (0)")
+    p.add_argument('--jsd', action='store_true', help="also report JSD (occupancy grid clipped to the unit sphere)")
+    p.add_argument('--jsd_resolution', type=int, default=28, help="grid resolution of --jsd (2 to 32)")
     p.add_argument('--device', type=str, default='cuda:0')
     p.add_argument('--save', type=str, default=None, help="write the metrics to this JSON file")
     return p
 
 
-def evaluate(samples, refs, device='cuda:0'):
-    """the six metrics (python floats) of the clouds samples (S, N, C) against refs (R, N', C), numpy arrays"""
+def evaluate(samples, refs, device='cuda:0', jsd_resolution=None):
+    """the six metrics (python floats) of the clouds samples (S, N, C) against refs (R, N', C), numpy arrays; with jsd_resolution
+    also 'JSD' on a grid of that resolution"""
     import torch
-    from metrics_point_cloud.generation_metrics import compute_all_metrics
+    from metrics_point_cloud.generation_metrics import compute_all_metrics, jsd_between_point_cloud_sets
     dev = torch.device(device)
     s = torch.from_numpy(np.ascontiguousarray(samples, dtype=np.float32)).to(dev)
     r = torch.from_numpy(np.ascontiguousarray(refs, dtype=np.float32)).to(dev)
     res = compute_all_metrics(s, r)
-    return {k: float(res[k]) for k in KEYS}
+    out = {k: float(res[k]) for k in KEYS}
+    if jsd_resolution is not None:
+        out["JSD"] = float(jsd_between_point_cloud_sets(s, r, jsd_resolution))
+    return out
 
 
 def main(argv=None):
@@ -58,10 +67,10 @@ def main(argv=None):
         refs = normalize_point_cloud(refs, bool(args.normalize_std_per_axis), bool(args.normalize_per_shape),
                                      input_dim=refs.shape[2])
     t0 = time.perf_counter()
-    res = evaluate(samples, refs, args.device)
+    res = evaluate(samples, refs, args.device, args.jsd_resolution if args.jsd else None)
     dt = time.perf_counter() - t0
     print('%d samples x %d references' % (samples.shape[0], refs.shape[0]))
-    for k in KEYS:
+    for k in KEYS + (("JSD",) if args.jsd else ()):
         print('%-16s %.9e' % (k, res[k]))
     print('wall time %.3f s' % dt)
     if args.save:

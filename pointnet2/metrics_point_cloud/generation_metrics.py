@@ -8,7 +8,18 @@ chamfer_and_f1.calc_cd gives for that pair (`cd_t`), wherever the pair sits in t
 
 Scope: CUDA tensors only for `pairwise_cd` / `compute_all_metrics` (no CPU fallback), no autograd (inputs that require grad raise
 NotImplementedError), fixed-size clouds (a set is a dense (M, P, C) tensor).  `lgan_mmd_cov` and `knn` are plain torch and run on
-any device.  The reference's EMD keys are absent: Earth Mover's Distance is not implemented in this project."""
+any device.  The reference's EMD keys are absent: Earth Mover's Distance is not implemented in this project.
+
+JSD block (`unit_cube_grid_point_cloud`, `entropy_of_occupancy_grid`, `jensen_shannon_divergence`, `jsd_between_point_cloud_sets`;
+the reference's names, argument lists, defaults and return types): the Jensen-Shannon divergence between the occupancy distributions
+of two sets on a resolution^3 grid clipped to the unit sphere.  The per-cloud nearest-cell query and the two counting loops of the
+reference are ONE launch of slide_amd/csrc/occupancy_grid.hip; the grid and its sphere mask are built here in numpy with the
+reference's expressions and uploaded, so the boundary cells are the reference's.  The entropy / JSD arithmetic runs over at most
+32 768 numbers on the host in float64 (no scipy).  Resolutions 2 to 32."""
+import functools
+import warnings
+
+import numpy as np
 import torch
 
 from slide_amd import _ext as _hip
@@ -115,3 +126,138 @@ def compute_all_metrics(sample_pcs, ref_pcs, batch_size=None):
         one_nn_cd_res = knn(M_rr_cd, M_rs_cd, M_ss_cd, 1, sqrt=False)
         results.update({"1-NN-CD-%s" % k: v for k, v in one_nn_cd_res.items() if 'acc' in k})
     return results
+
+
+#######################################################
+# JSD : occupancy grids (Achlioptas et al., "Learning Representations and Generative Models for 3D Point Clouds")
+#######################################################
+@functools.lru_cache(maxsize=8)
+def _grid_axis_and_mask(resolution, clip_sphere):
+    """(axis (R,) float32, grid (R^3, 3) float32, mask (R^3,) bool): a cell-centre coordinate is `i * spacing - 0.5` evaluated in
+    double and rounded once to float32; the sphere mask is numpy's float32 norm of the float32 grid against 0.5"""
+    resolution = int(resolution)
+    spacing = 1.0 / float(resolution - 1)
+    axis = (np.arange(resolution, dtype=np.float64) * spacing - 0.5).astype(np.float32)
+    gi, gj, gk = np.meshgrid(axis, axis, axis, indexing="ij")
+    grid = np.stack((gi, gj, gk), axis=-1).reshape(-1, 3)
+    mask = (np.linalg.norm(grid, axis=1) <= 0.5) if clip_sphere else np.ones(len(grid), bool)
+    for a in (axis, grid, mask):
+        a.setflags(write=False)
+    return axis, grid, mask
+
+
+def unit_cube_grid_point_cloud(resolution, clip_sphere=False):
+    """Returns the center coordinates of each cell of a 3D grid with resolution^3 cells, that is placed in the unit-cube:
+    (grid, spacing), grid float32 (resolution, resolution, resolution, 3), or with clip_sphere the (n, 3) cells that lie inside the
+    unit sphere (norm <= 0.5) in flattened order."""
+    _, grid, mask = _grid_axis_and_mask(int(resolution), bool(clip_sphere))
+    spacing = 1.0 / float(resolution - 1)
+    if clip_sphere:
+        return grid[mask], spacing
+    return grid.reshape(resolution, resolution, resolution, 3).copy(), spacing
+
+
+def _bernoulli_entropy_sum(rvars, n):
+    """sum over the cells with g > 0 of the entropy (natural log) of a Bernoulli variable with p = g / n:
+    -(p ln p + (1 - p) ln(1 - p)), the second term 0 at p = 1"""
+    g = np.asarray(rvars, np.float64)
+    p = g[g > 0] / float(n)
+    q = 1.0 - p
+    with np.errstate(divide="ignore", invalid="ignore"):
+        h = -(p * np.log(p)) - np.where(q > 0, q * np.log(q), 0.0)
+    return float(np.sum(h))
+
+
+def occupancy_counters(pclouds, grid_resolution, in_sphere=False):
+    """(grid_counters, grid_bernoulli_rvars) of the reference's entropy_of_occupancy_grid: float64 arrays over the admissible
+    cells in flattened order -- points per cell over all clouds, and clouds with at least one point in the cell.  One launch."""
+    if not 2 <= int(grid_resolution) <= 32:
+        raise ValueError("grid_resolution must be in [2, 32], got %r" % (grid_resolution,))
+    pts = _as_device_clouds(pclouds)
+    axis, _, mask = _grid_axis_and_mask(int(grid_resolution), bool(in_sphere))
+    counts, clouds = _hip.occupancy_grid(pts, torch.tensor(axis), torch.tensor(mask))  # (copies: the cached arrays are read-only)
+    both = torch.stack((counts, clouds)).cpu().numpy()
+    return both[0][mask].astype(np.float64), both[1][mask].astype(np.float64)
+
+
+def _as_device_clouds(pclouds):
+    if torch.is_tensor(pclouds):
+        if not pclouds.is_cuda:
+            raise RuntimeError("metrics_point_cloud.generation_metrics runs on the GPU only: got a %s tensor" % pclouds.device)
+        t = pclouds.detach()
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(pclouds)).to(torch.device("cuda", torch.cuda.current_device()))
+    if t.ndim != 3 or t.shape[2] < 3:
+        raise ValueError("Expected pclouds of shape (#point-clouds, points per point-cloud, 3)")
+    return t.float()
+
+
+def entropy_of_occupancy_grid(pclouds, grid_resolution, in_sphere=False, verbose=False):
+    """Given a collection of point-clouds, estimate the entropy of the random variables corresponding to occupancy-grid activation
+    patterns.  pclouds: #point-clouds x points per point-cloud x 3, a CUDA tensor or a numpy array (moved to the current device).
+    -> (mean Bernoulli entropy per cell (float), grid_counters: numpy float64, one per admissible cell in flattened order)."""
+    pts = _as_device_clouds(pclouds)
+    epsilon = 10e-4
+    bound = 0.5 + epsilon
+    if verbose and pts.numel():
+        xyz = pts[:, :, :3]
+        if abs(float(xyz.max())) > bound or abs(float(xyz.min())) > bound:
+            warnings.warn('Point-clouds are not in unit cube.')
+        if in_sphere and float(xyz.pow(2).sum(2).sqrt().max()) > bound:
+            warnings.warn('Point-clouds are not in unit sphere.')
+    grid_counters, grid_bernoulli_rvars = occupancy_counters(pts, grid_resolution, in_sphere)
+    acc_entropy = _bernoulli_entropy_sum(grid_bernoulli_rvars, len(pts)) if len(pts) else 0.0
+    return acc_entropy / len(grid_counters), grid_counters
+
+
+def _entropy_base2(p):
+    """-sum p log2 p of a float64 vector that sums to one (zero entries contribute 0)"""
+    p = p[p > 0]
+    return float(-np.sum(p * np.log(p)) / np.log(2.0))
+
+
+def jensen_shannon_divergence(P, Q):
+    P, Q = np.asarray(P), np.asarray(Q)
+    if np.any(P < 0) or np.any(Q < 0):
+        raise ValueError('Negative values.')
+    if len(P) != len(Q):
+        raise ValueError('Non equal size.')
+
+    P_ = P / np.sum(P)  # Ensure probabilities.
+    Q_ = Q / np.sum(Q)
+
+    e1 = _entropy_base2(P_)
+    e2 = _entropy_base2(Q_)
+    e_sum = _entropy_base2((P_ + Q_) / 2.0)
+    res = e_sum - ((e1 + e2) / 2.0)
+
+    res2 = _jsdiv(P_, Q_)
+
+    if not np.allclose(res, res2, atol=10e-5, rtol=0):
+        warnings.warn('Numerical values of two JSD methods don\'t agree.')
+
+    return res
+
+
+def _jsdiv(P, Q):
+    """another way of computing JSD: the mean of the two Kullback-Leibler divergences (base 2) to the mixture"""
+
+    def _kldiv(A, B):
+        idx = np.logical_and(A > 0, B > 0)
+        a, b = A[idx], B[idx]
+        return float(np.sum(a * np.log2(a / b)))
+
+    P_ = P / np.sum(P)
+    Q_ = Q / np.sum(Q)
+    M = 0.5 * (P_ + Q_)
+    return 0.5 * (_kldiv(P_, M) + _kldiv(Q_, M))
+
+
+def jsd_between_point_cloud_sets(sample_pcs, ref_pcs, resolution=28):
+    """Computes the JSD between two sets of point-clouds, as introduced in the paper ```Learning Representations And Generative
+    Models For 3D Point Clouds```.  sample_pcs (S1, R1, 3), ref_pcs (S2, R2, 3): CUDA tensors or numpy arrays; resolution: the
+    grid resolution (2 to 32).  The grid is clipped to the unit sphere; a point goes to its nearest cell inside it."""
+    in_unit_sphere = True
+    sample_grid_var = entropy_of_occupancy_grid(sample_pcs, resolution, in_unit_sphere)[1]
+    ref_grid_var = entropy_of_occupancy_grid(ref_pcs, resolution, in_unit_sphere)[1]
+    return jensen_shannon_divergence(sample_grid_var, ref_grid_var)

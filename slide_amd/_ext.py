@@ -347,3 +347,42 @@ def chamfer_pairwise(x, y=None):
     check(lib().slide_chamfer_pairwise(M, N, P, Q, ptr(x), sx, ptr(y), sy, int(symmetric), ptr(out), stream_of()),
           "chamfer_pairwise")
     return out
+
+
+def occupancy_grid(points, axis, mask, return_cells=False):
+    """occupancy counters of a set of clouds on an R^3 lattice in one launch (include/slide_hip.h slide_occupancy_grid): points
+    (S,P,C>=3) f32 CUDA tensor (xyz = channels 0:3, read in place), axis (R,) f32 cell-centre coordinates of one axis (strictly
+    ascending, 2 <= R <= 32), mask R^3 admissibility flags (bool / uint8, any shape of R^3 elements, flat index (i R + j) R + k)
+    -> (counts (R^3,) int32: points whose nearest admissible cell is c, clouds (R^3,) int32: clouds with at least one such point);
+    with return_cells also cells (S,P) int32, every point's cell.  axis and mask may be host tensors (they are uploaded).
+    ValueError for a non-finite coordinate or a mask without an admissible cell (one host read of a flag word)."""
+    points, sp = _pts3(points, "points")
+    dev = points.device
+    axis = torch.as_tensor(axis)
+    if axis.dtype != torch.float32 or axis.dim() != 1:
+        raise RuntimeError("axis must be a 1-D float tensor")
+    R = axis.numel()
+    if not 2 <= R <= 32:
+        raise ValueError("the grid resolution must be in [2, 32], got %d" % R)
+    mask = torch.as_tensor(mask)
+    if mask.numel() != R ** 3 or mask.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError("mask must hold R^3 = %d bool / uint8 flags" % R ** 3)
+    S, P = points.size(0), points.size(1)
+    if S * P > 2 ** 31 - 1:
+        raise ValueError("occupancy_grid counts in 32 bits: at most 2^31 - 1 points per call")
+    axis = axis.to(dev).contiguous()
+    # a row of cells -> one word, bit k = cell (i, j, k)
+    rowmask = ((mask.to(dev).reshape(R * R, R) != 0).long() << torch.arange(R, device=dev)).sum(1).to(torch.int32).contiguous()
+    counts = torch.zeros(R ** 3, device=dev, dtype=torch.int32)
+    clouds = torch.zeros(R ** 3, device=dev, dtype=torch.int32)
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    cells = torch.empty((S, P), device=dev, dtype=torch.int32) if return_cells else None
+    check(lib().slide_occupancy_grid(S, P, ptr(points), sp, R, ptr(axis), ptr(rowmask), ptr(counts), ptr(clouds),
+                                     None if cells is None else ptr(cells), ptr(flag), stream_of()), "occupancy_grid")
+    if S and P:
+        f = int(flag.item())
+        if f & 1:
+            raise ValueError("occupancy_grid: points holds a non-finite coordinate")
+        if f & 2:
+            raise ValueError("occupancy_grid: the mask admits no cell")
+    return (counts, clouds, cells) if return_cells else (counts, clouds)
