@@ -28,29 +28,37 @@ extern "C" {
 /* y = post_relu?(GroupNorm_G(pre_relu?(x))) on [B*S][ld]: the first n_norm channels in G <= 64 groups over (group x S rows of a
  * sample), the rest pass through (MyGroupNorm); flags: 1 = ReLU before, 2 = ReLU after.  G = 0: no normalisation (ReLUs only;
  * gamma, beta, mean_rstd, dgamma, dbeta, scratch may be NULL).  mean_rstd [B][64][2]: the forward's statistics
- * (SLIDE_OP_ROWS_GN p[10], slide_engine.h).  Writes dx [B*S][ld] and the PER-SAMPLE parameter gradients dgamma, dbeta [B][ld]
- * (zero beyond n_norm; the caller sums over B: a deterministic reduction).  scratch: B * (64 * ld * 2 + 128) floats. */
+ * (SLIDE_OP_ROWS_GN p[10], slide_engine.h).  Writes dx [B*S][ld] in full, pad columns included (there dx = dy, masked by x > 0
+ * when a ReLU is set) and, with G > 0, the PER-SAMPLE parameter gradients dgamma, dbeta [B][ld] in full (zero beyond n_norm; the
+ * caller sums over B: a deterministic reduction); with G = 0 dgamma and dbeta are not touched.  scratch: B * (64 * ld * 2 + 128)
+ * floats.  B <= 0 or S <= 0: 0 without a launch.  -3, nothing written: ld not a positive multiple of 32 up to 1024, G outside
+ * 0..64, n_norm outside 0..ld or no multiple of G, G = 0 with n_norm != 0, or G > 0 with a NULL among the six pointers above. */
 SLIDE_API int slide_gn_rows_bwd(int B, int S, int ld, int G, int n_norm, int flags, const float *x, const float *gamma,
                                 const float *beta, const float *mean_rstd, const float *dy, float *dx, float *dgamma, float *dbeta,
                                 float *scratch, slide_stream_t stream);
 
 /* out [ld] = column sums of x [rows][ld] (the bias gradient of a convolution: the sum of dy over the rows; GroupNorm's parameter
- * gradients over the batch).  Two launches: row chunks, then 32-column stripes over the partial rows; deterministic.
- * scratch: 1024 * ld floats (unused when rows < 128). */
+ * gradients over the batch); out is written in full (rows = 0: zeros).  rows < 128: one launch of 32-column stripes, scratch
+ * unused (may be NULL).  rows >= 128: two launches, up to 1024 row chunks into scratch (1024 * ld floats), then 32-column stripes
+ * over the partial rows.  Deterministic.  -3, nothing written: ld not a positive multiple of 32 up to 1024, rows < 0, or
+ * rows >= 128 with scratch NULL. */
 SLIDE_API int slide_col_sums(long long rows, int ld, const float *x, float *out, float *scratch, slide_stream_t stream);
 
 /* grouped rows out[(b,p,k)][0..C) = feat[b][idx[b][p][k]][0..C): dfeat [B*N][ldf] += dout [B*np*K][ldg] (atomic; dfeat must be
- * zero-initialised); counts (B*np) int32 or NULL: centres with count 0 carried zero features and receive nothing. */
+ * zero-initialised); counts (B*np) int32 or NULL: centres with count 0 carried zero features and receive nothing.  Only the
+ * elements that a gradient row lands on are touched: channels >= C and rows that no live centre indexes keep their value. */
 SLIDE_API int slide_group_rows_bwd(int B, int N, int np, int K, int C, int ldf, int ldg, const int64_t *idx, const int *counts,
                                    const float *dout, float *dfeat, slide_stream_t stream);
 
 /* out = relu([q(point) broadcast over K | k(point, neighbour)]) with q [pts][ldq] (C1 channels), k [pts*K][ldk] (C2), out
- * [pts*K][ldo]: dq, dk from dout and the forward OUTPUT (the ReLU mask); the first C1 / C2 channels of dq / dk are written. */
+ * [pts*K][ldo]: dq, dk from dout and the forward OUTPUT (the ReLU mask); the first C1 / C2 channels of dq / dk are written, their
+ * pad columns are not touched (the caller zeroes them).  dk is a masked move; dq adds its K terms in ascending k: deterministic. */
 SLIDE_API int slide_concat_qk_bwd(long long pts, int K, int C1, int ldq, int C2, int ldk, int ldo, const float *out,
                                   const float *dout, float *dq, float *dk, slide_stream_t stream);
 
 /* out[pt][c] = sum_k softmax_k(s)[k][c] v[(pt,k)][c] over the first max(1, count) of the K neighbour rows (counts NULL: all K):
- * ds, dv [pts*K][lds | ldv] (first C channels) from s, v and dout [pts][ldo]. */
+ * ds, dv [pts*K][lds | ldv] from s, v and dout [pts][ldo].  The first C channels of all K rows of a point are written: rows past
+ * the count are WRITTEN as 0 in ds and dv; columns >= C are not touched (the caller zeroes them). */
 SLIDE_API int slide_attn_rows_bwd(long long pts, int K, int C, int lds, int ldv, int ldo, const float *s, const float *v,
                                   const int *counts, const float *dout, float *ds, float *dv, slide_stream_t stream);
 

@@ -309,7 +309,7 @@ int slide_gn_rows_bwd(int B, int S, int ld, int G, int n_norm, int flags, const 
                       const float *mean_rstd, const float *dy, float *dx, float *dgamma, float *dbeta, float *scratch,
                       slide_stream_t stream) {
   if (B <= 0 || S <= 0) return 0;
-  if (ld % 32 || ld > 1024 || G < 0 || G > 64 || n_norm < 0 || n_norm > ld || (G > 0 && n_norm % G) || (G == 0 && n_norm != 0)) return -3;
+  if (ld <= 0 || ld % 32 || ld > 1024 || G < 0 || G > 64 || n_norm < 0 || n_norm > ld || (G > 0 && n_norm % G) || (G == 0 && n_norm != 0)) return -3;
   if (G > 0 && (!mean_rstd || !scratch || !gamma || !beta || !dgamma || !dbeta)) return -3;
   const int rt = 256 / (ld / 4);
   int nchunk = (S + rt * 4 - 1) / (rt * 4);
@@ -330,7 +330,7 @@ int slide_gn_rows_bwd(int B, int S, int ld, int G, int n_norm, int flags, const 
 }
 
 int slide_col_sums(long long rows, int ld, const float *x, float *out, float *scratch, slide_stream_t stream) {
-  if (ld % 32 || ld > 1024 || rows < 0) return -3;
+  if (ld <= 0 || ld % 32 || ld > 1024 || rows < 0) return -3;
   long long nchunk = rows / 64;
   nchunk = nchunk < 1 ? 1 : nchunk > 1024 ? 1024 : nchunk;
   const int rpc = (int)((rows + nchunk - 1) / nchunk);

@@ -780,20 +780,26 @@ _FORWARD = dict(from_ncx=_from_ncx, to_ncx=_to_ncx, group=_group, gn=_gn, gn_joi
                 pool=_pool, pair_expand=_pair_expand)
 
 
+def store(o, half):
+    """the store term of an output dict(y, b): adds `stored` (y rounded to the stored type) and widens b where it is not 0 (exact)"""
+    y = o["y"]
+    b = np.broadcast_to(np.asarray(o["b"], np.float64), y.shape)
+    with np.errstate(invalid="ignore", over="ignore"):
+        if half:
+            o["stored"] = r16(y)
+            o["b"] = np.where(b > 0, b * (1 + 2.0 ** -11) + 2.0 ** -11 * np.abs(y) + 2.0 ** -25, 0.0)
+        else:
+            o["stored"] = r32(y)
+            o["b"] = np.where(b > 0, b + U * np.abs(y), 0.0)
+    return o
+
+
 def forward(c, d, mutant=None):
     """float64 reference of the case (or of one of its mutants): {output name: dict(y, b, stored)}; b already holds the store
     term of the output's type, and is 0 where the element must be exact"""
     outs = _FORWARD[c["op"]](c, d, mutant)
     for o in outs.values():
-        y = o["y"]
-        b = np.broadcast_to(np.asarray(o["b"], np.float64), y.shape)
-        with np.errstate(invalid="ignore", over="ignore"):
-            if o.get("typ", "rows") == "rows" and c["half"]:
-                o["stored"] = r16(y)
-                o["b"] = np.where(b > 0, b * (1 + 2.0 ** -11) + 2.0 ** -11 * np.abs(y) + 2.0 ** -25, 0.0)
-            else:
-                o["stored"] = r32(y)
-                o["b"] = np.where(b > 0, b + U * np.abs(y), 0.0)
+        store(o, o.get("typ", "rows") == "rows" and c["half"])
     return outs
 
 
