@@ -50,6 +50,26 @@ SLIDE_API int slide_col_sums(long long rows, int ld, const float *x, float *out,
 SLIDE_API int slide_group_rows_bwd(int B, int N, int np, int K, int C, int ldf, int ldg, const int64_t *idx, const int *counts,
                                    const float *dout, float *dfeat, slide_stream_t stream);
 
+/* Backward of the COORDINATE columns of the grouped rows (SLIDE_OP_ROWS_GROUP; flags and column orders are the forward's):
+ * dout [B*np*K][ldg] -> dxyz [B][N][3] (source points) and dnew_xyz [B][np][3] (centres); the reference differentiates them in
+ * QueryAndGroup (pointnet2_utils.py:383-408) and group_knn (:506-520).  Row (b, p, k): q = xyz[b][idx[b][p][k]], c = new_xyz[b][p].
+ *   SA form (flags & 1 == 0), columns C.. = rel, abs if flags & 2, centre if flags & 4:   dq += g_rel + g_abs,  dc += -g_rel + g_ctr
+ *     (flags & 8: no coordinate columns, 0 without a launch)
+ *   FP form (flags & 1), columns C.. = d2, w, abs(3), rel(3), centre(3); d2 [B][np][K] is the array the forward was given and is
+ *     differentiated as |q - c|^2:  r_k = 1 / (d2_k + 1e-8), S = sum_k r_k, w_k = r_k / S,
+ *     G_k = g_d2_k - (r_k^2 / S) (g_w_k - sum_j g_w_j w_j),  v_k = 2 G_k (q_k - c),
+ *     dq_k += v_k + g_abs_k + g_rel_k,  dc += sum_k (-v_k - g_rel_k + g_ctr_k)
+ * flags & 16: idx is int32, else int64.  counts (B*np int32) or NULL: a centre with count 0 was its own neighbour -- abs feeds dc,
+ * rel contributes nothing, no source point is touched.
+ * dnew_xyz is written in full, every element once, its K terms added in ascending k: deterministic, independent of the batch
+ * position.  dxyz is ACCUMULATED with fp32 atomics (three per row) into a buffer the caller zeroes: not bit-reproducible.  Either
+ * output may be NULL (not computed); both NULL: 0 without a launch.  B, N or np <= 0: 0 without a launch.  -3, nothing written: ld
+ * not a positive multiple of 32 up to 1024, C < 0, C + the coordinate column count > ldg, K < 1, a NULL among xyz, new_xyz, idx,
+ * dout, or the FP form with d2 NULL. */
+SLIDE_API int slide_group_rows_coord_bwd(int B, int N, int np, int K, int C, int ldg, int flags, const float *xyz,
+                                         const float *new_xyz, const void *idx, const float *d2, const int *counts, const float *dout,
+                                         float *dxyz, float *dnew_xyz, slide_stream_t stream);
+
 /* out = relu([q(point) broadcast over K | k(point, neighbour)]) with q [pts][ldq] (C1 channels), k [pts*K][ldk] (C2), out
  * [pts*K][ldo]: dq, dk from dout and the forward OUTPUT (the ReLU mask); the first C1 / C2 channels of dq / dk are written, their
  * pad columns are not touched (the caller zeroes them).  dk is a masked move; dq adds its K terms in ascending k: deterministic. */

@@ -25,7 +25,8 @@ UNROLL = ["-mllvm", "-pragma-unroll-threshold=100000"]
 SOURCES = [("point_ops.hip", ["-ffp-contract=off"]), ("chamfer.hip", ["-ffp-contract=off"]),
            ("chamfer_pairwise.hip", ["-ffp-contract=off"]), ("chamfer_bwd.hip", ["-ffp-contract=off"]),
            ("occupancy_grid.hip", ["-ffp-contract=off"]), ("engine.hip", UNROLL), ("gemm_gx.hip", UNROLL), ("gemm_gxs.hip", UNROLL),
-           ("point_chain.hip", UNROLL), ("rows_ops.hip", []), ("train_ops.hip", [])]
+           ("point_chain.hip", UNROLL), ("rows_ops.hip", []), ("train_ops.hip", []),
+           ("group_coord_bwd.hip", ["-ffp-contract=off"])]
 SOURCES_EXP = SOURCES + [("experiments/block_body.hip", UNROLL), ("experiments/gemm_xs.hip", UNROLL), ("experiments/gemm_chain.hip", UNROLL),
                          ("experiments/resident.hip", UNROLL)]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",

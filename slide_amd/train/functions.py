@@ -13,8 +13,8 @@ from torch.autograd.function import once_differentiable
 from .. import _ext
 from .._lib import check, lib
 from ..engine import EPI_RAW, OP_GEMM, SlideEpi, make_op, ru
-from ..rows import (GN_POST_RELU, GN_PRE_RELU, GROUP_ABS, GROUP_CENTER, GROUP_FP, OP_ROWS_ATTN, OP_ROWS_CONCAT_QK, OP_ROWS_GN,
-                    OP_ROWS_GROUP, _rop, _run)
+from ..rows import (GN_POST_RELU, GN_PRE_RELU, GROUP_ABS, GROUP_CENTER, GROUP_FP, GROUP_IDX32, GROUP_NO_XYZ, OP_ROWS_ATTN,
+                    OP_ROWS_CONCAT_QK, OP_ROWS_GN, OP_ROWS_GROUP, _rop, _run)
 
 PREC_SPLIT = 2
 _c = ctypes.c_void_p
@@ -211,33 +211,64 @@ class GroupNormRows(torch.autograd.Function):
 
 
 class GroupRows(torch.autograd.Function):
-    """grouped input of an SA block (QueryAndGroup 'nn': [feat | rel | abs | centre]) or of a kNN feature-propagation block
-    (group_knn: [feat | d2 | w | abs | rel | centre]) as rows [(b, p, k)]; differentiable in the FEATURES only (the coordinates are
-    network inputs, pointnet2_utils.py:383-430, :497-524)"""
+    """grouped input of an SA block (QueryAndGroup: [feat | rel | abs | centre]) or of a kNN feature-propagation block
+    (group_knn: [feat | d2 | w | abs | rel | centre]) as rows [(b, p, k)] (pointnet2_utils.py:383-430, :497-524); differentiable in the
+    features and -- for given neighbours -- in both coordinate tensors (csrc/group_coord_bwd.hip; d2 is differentiated as the squared
+    distance of the pair).  feat None: C = 0.  idx int64 (knn_points) or int32 (ball_query); counts (B, np) int32 or None: a centre
+    with count 0 is its own neighbour, with zero features.  With coordinates that do not require grad nothing is saved for them and
+    the coordinate kernel is not launched."""
 
     @staticmethod
-    def forward(ctx, feat, xyz, new_xyz, idx, d2, flags, C):
-        _chk(feat)
+    def forward(ctx, feat, xyz, new_xyz, idx, d2, flags, C, counts=None):
+        if feat is not None:
+            _chk(feat)
+        elif not xyz.is_cuda:
+            raise RuntimeError("CPU not supported: the training layers launch HIP kernels")
         B, N = xyz.shape[:2]
         npnt, K = idx.shape[1:]
-        ncoord = 11 if flags & GROUP_FP else 3 + (3 if flags & GROUP_ABS else 0) + (3 if flags & GROUP_CENTER else 0)
-        out = torch.empty(B * npnt * K, ru(C + ncoord), device=feat.device, dtype=torch.float32)
+        flags = (flags & ~GROUP_IDX32) | (GROUP_IDX32 if idx.dtype == torch.int32 else 0)
+        ncoord = 11 if flags & GROUP_FP else 0 if flags & GROUP_NO_XYZ else 3 + (3 if flags & GROUP_ABS else 0) + (3 if flags & GROUP_CENTER else 0)
+        ldf = 0 if feat is None else feat.shape[1]
+        # (GROUP_NO_XYZ keeps the width it always had here: room for the rel columns, left zero)
+        out = torch.empty(B * npnt * K, ru(C + max(ncoord, 3)), device=xyz.device, dtype=torch.float32)
         idx = idx.contiguous()
-        assert idx.dtype == torch.int64 and feat.shape[0] == B * N
-        _run(_rop(OP_ROWS_GROUP, False, (B, N, npnt, K, C, feat.shape[1], out.shape[1], flags),
-                  (xyz.contiguous().float(), new_xyz.contiguous().float(), feat, idx, None if d2 is None else d2.contiguous(), out, None)))
-        ctx.save_for_backward(idx)
-        ctx.cfg = (B, N, npnt, K, C, feat.shape[1], out.shape[1])
+        assert idx.dtype in (torch.int64, torch.int32) and (feat is None or feat.shape[0] == B * N) and (feat is not None or C == 0)
+        assert counts is None or (counts.dtype == torch.int32 and counts.shape == (B, npnt))
+        need_coord = ncoord > 0 and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        if need_coord and (xyz.dtype != torch.float32 or new_xyz.dtype != torch.float32):
+            raise RuntimeError("the coordinate gradient of the grouping layer takes float32 coordinates")
+        xyz_c, new_c = xyz.contiguous().float(), new_xyz.contiguous().float()
+        d2 = None if d2 is None else d2.contiguous()
+        counts = None if counts is None else counts.contiguous()
+        _run(_rop(OP_ROWS_GROUP, False, (B, N, npnt, K, C, ldf, out.shape[1], flags), (xyz_c, new_c, feat, idx, d2, out, counts)))
+        # (slide_group_rows_bwd reads int64 indices)
+        idx64 = idx.long() if feat is not None and idx.dtype == torch.int32 and ctx.needs_input_grad[0] else None
+        if need_coord:
+            ctx.save_for_backward(idx, idx64, counts, xyz_c, new_c, d2)
+        else:
+            ctx.save_for_backward(idx, idx64, counts)
+        ctx.cfg = (B, N, npnt, K, C, ldf, out.shape[1], flags, need_coord)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        (idx,) = ctx.saved_tensors
-        B, N, npnt, K, C, ldf, ldg = ctx.cfg
+        idx, idx64, counts = ctx.saved_tensors[:3]
+        B, N, npnt, K, C, ldf, ldg, flags, need_coord = ctx.cfg
         dout = dout.contiguous()
-        dfeat = torch.zeros(B * N, ldf, device=dout.device, dtype=torch.float32)
-        check(lib().slide_group_rows_bwd(B, N, npnt, K, C, ldf, ldg, _p(idx), None, _p(dout), _p(dfeat), _stream()), "slide_group_rows_bwd")
-        return dfeat, None, None, None, None, None, None
+        dfeat = dxyz = dnew = None
+        if ldf and ctx.needs_input_grad[0]:
+            dfeat = torch.zeros(B * N, ldf, device=dout.device, dtype=torch.float32)
+            check(lib().slide_group_rows_bwd(B, N, npnt, K, C, ldf, ldg, _p(idx if idx64 is None else idx64), _p(counts), _p(dout), _p(dfeat),
+                                             _stream()), "slide_group_rows_bwd")
+        if need_coord:
+            xyz, new_xyz, d2 = ctx.saved_tensors[3:]
+            if ctx.needs_input_grad[1]:
+                dxyz = torch.zeros(B, N, 3, device=dout.device, dtype=torch.float32)  # (accumulated with atomics)
+            if ctx.needs_input_grad[2]:
+                dnew = torch.empty(B, npnt, 3, device=dout.device, dtype=torch.float32)  # (written in full)
+            check(lib().slide_group_rows_coord_bwd(B, N, npnt, K, C, ldg, flags, _p(xyz), _p(new_xyz), _p(idx), _p(d2), _p(counts), _p(dout),
+                                                   _p(dxyz), _p(dnew), _stream()), "slide_group_rows_coord_bwd")
+        return dfeat, dxyz, dnew, None, None, None, None, None
 
 
 class ConcatQK(torch.autograd.Function):
@@ -349,8 +380,8 @@ def gn_rows(x, gamma, beta, B, S, G, pre_relu=False, post_relu=False):
     return GroupNormRows.apply(x, gamma, beta, B, S, G, pre_relu, post_relu)
 
 
-def group_rows(feat, xyz, new_xyz, idx, d2, flags, C):
-    return GroupRows.apply(feat, xyz, new_xyz, idx, d2, flags, C)
+def group_rows(feat, xyz, new_xyz, idx, d2, flags, C, counts=None):
+    return GroupRows.apply(feat, xyz, new_xyz, idx, d2, flags, C, counts)
 
 
 def concat_qk(q, k, K, C1, C2):
