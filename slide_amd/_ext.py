@@ -7,11 +7,11 @@ hand-written gfx950 HIP kernels through the C-ABI in include/slide_hip.h.
 
 Asynchronous on torch's current stream, no host sync, inputs borrowed and never mutated.
 """
-import ctypes
 
 import torch
 
-from ._lib import check, lib, ptr, stream_of
+from ._lib import check, lib
+from .abi import CHAMFER_TERM, ptr, stream_of
 
 
 def _chk_contig(x, name):
@@ -128,7 +128,7 @@ def ball_query(new_xyz, xyz, radius, nsample):
     idx = torch.zeros((new_xyz.size(0), new_xyz.size(1), nsample), device=new_xyz.device, dtype=torch.int32)
     counts = torch.zeros((new_xyz.size(0), new_xyz.size(1)), device=new_xyz.device, dtype=torch.int32)
     _need_gpu(new_xyz)
-    check(lib().query_ball_point_kernel_wrapper(xyz.size(0), xyz.size(1), new_xyz.size(1), ctypes.c_float(radius),
+    check(lib().query_ball_point_kernel_wrapper(xyz.size(0), xyz.size(1), new_xyz.size(1), radius,
                                                 int(nsample), ptr(new_xyz), ptr(xyz), ptr(idx), ptr(counts),
                                                 stream_of()), "ball_query")
     return idx, counts
@@ -267,9 +267,6 @@ def chamfer_nn(x, y, x_lengths=None, y_lengths=None):
     return d1, i1, d2, i2
 
 
-CHAMFER_TERM = {None: 0, "mse": 1, "cos": 2}
-
-
 def chamfer_reduce(d1, i1, d2, i2, x_lengths=None, y_lengths=None, threshold=1e-4, fx=None, fy=None, term=None):
     """per-cloud sums of chamfer_nn's output over the valid points, in a fixed order -> (B, 2, 5) f32:
     [pair][direction] = (sum d, sum sqrt d, count d < threshold, sum term, sum sqrt term).  fx (B,P1,F) / fy (B,P2,F) per-point
@@ -296,7 +293,7 @@ def chamfer_reduce(d1, i1, d2, i2, x_lengths=None, y_lengths=None, threshold=1e-
     lx, lxp = _lengths_ptr(x_lengths, d1.device)
     ly, lyp = _lengths_ptr(y_lengths, d1.device)
     out = torch.empty((B, 2, 5), device=d1.device, dtype=torch.float32)
-    check(lib().slide_chamfer_reduce(B, P1, P2, ptr(d1), pi1, ptr(d2), pi2, lxp, lyp, ctypes.c_float(threshold), F, mode,
+    check(lib().slide_chamfer_reduce(B, P1, P2, ptr(d1), pi1, ptr(d2), pi2, lxp, lyp, threshold, F, mode,
                                      pfx, sfx, pfy, sfy, ptr(out), stream_of()), "chamfer_reduce")
     return out
 
@@ -322,7 +319,7 @@ def chamfer_cd_bwd(x, y, d1, i1, d2, i2, dred, need_dx=True, need_dy=True):
     dx = torch.empty((B, P1, C), device=x.device, dtype=torch.float32) if need_dx else None
     dy = torch.empty((B, P2, C), device=x.device, dtype=torch.float32) if need_dy else None
     check(lib().slide_chamfer_cd_bwd(B, P1, P2, C - 3, ptr(x), sx, ptr(y), sy, ptr(d1), ptr(i1), ptr(d2), ptr(i2), ptr(dred),
-                                     None if dx is None else ptr(dx), None if dy is None else ptr(dy), stream_of()),
+                                     ptr(dx), ptr(dy), stream_of()),
           "chamfer_cd_bwd")
     return dx, dy
 
@@ -378,7 +375,7 @@ def occupancy_grid(points, axis, mask, return_cells=False):
     flag = torch.zeros(1, device=dev, dtype=torch.int32)
     cells = torch.empty((S, P), device=dev, dtype=torch.int32) if return_cells else None
     check(lib().slide_occupancy_grid(S, P, ptr(points), sp, R, ptr(axis), ptr(rowmask), ptr(counts), ptr(clouds),
-                                     None if cells is None else ptr(cells), ptr(flag), stream_of()), "occupancy_grid")
+                                     ptr(cells), ptr(flag), stream_of()), "occupancy_grid")
     if S and P:
         f = int(flag.item())
         if f & 1:

@@ -1,7 +1,9 @@
-"""ctypes binding of libslide_hip.so (include/slide_hip.h).  There is NO CPU fallback: if the HIP
-library is missing or fails to load, every op raises."""
+"""Loader of libslide_hip.so: opens the library and gives every function its prototype from abi.PROTOTYPES (the Python statement
+of include/*.h).  There is NO CPU fallback: if the HIP library is missing or fails to load, every op raises."""
 import ctypes
 import os
+
+from . import abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SLIDE_HIP_LIB: developer knob for A/B timing of two builds of the same library (tools/ab/ab_build.sh)
@@ -11,15 +13,9 @@ LIB_PATH = os.environ.get("SLIDE_HIP_LIB") or os.path.join(_HERE, "libslide_hip.
 LIB_EXP_PATH = os.path.join(_HERE, "libslide_hip_exp.so")
 _libs = {}
 _use_exp = [os.environ.get("SLIDE_EXPERIMENTS", "0") not in ("", "0")]
-ST_EXPERIMENT = -20  # status of an op whose kernel is not in the product library (csrc/engine.hip)
-
-EXPORTS = [
-    "gather_points_kernel_wrapper", "gather_points_grad_kernel_wrapper",
-    "furthest_point_sampling_kernel_wrapper", "query_ball_point_kernel_wrapper",
-    "group_points_kernel_wrapper", "group_points_grad_kernel_wrapper", "three_nn_kernel_wrapper",
-    "three_interpolate_kernel_wrapper", "three_interpolate_grad_kernel_wrapper", "slide_knn_points",
-    "slide_knn_gather", "slide_gather_rows", "slide_chamfer_nn", "slide_chamfer_reduce", "slide_chamfer_pairwise", "slide_chamfer_cd_bwd", "slide_group_rows_coord_bwd", "slide_occupancy_grid", "slide_sample_farthest_points", "slide_hip_version", "slide_hip_device_ok",
-]
+# the names include/slide_hip.h, slide_engine.h and slide_train.h declare (the experiments header's are not in the product library)
+EXPORTS = sorted(n for n in abi.PROTOTYPES if n not in abi.EXPERIMENT_FUNCTIONS)
+ST_EXPERIMENT, ptr, stream_of = abi.ST_EXPERIMENT, abi.ptr, abi.stream_of
 
 
 class SlideHipError(RuntimeError):
@@ -32,9 +28,8 @@ def _load(path):
             raise SlideHipError(
                 "%s is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `python slide_amd/build.py [--experiments]`; there is no CPU fallback." % (os.path.basename(path), path))
-        h = ctypes.CDLL(path)
-        h.slide_hip_version.restype = ctypes.c_char_p
-        _libs[path] = h
+        # every function gets its prototype (abi.PROTOTYPES): pointers and long long row counts then cross at full width
+        _libs[path] = abi.bind(ctypes.CDLL(path), experiments=path == LIB_EXP_PATH)
     return _libs[path]
 
 
@@ -68,12 +63,3 @@ def check(status, what):
                             "SLIDE_EXPERIMENTS=1" % what)
     if status != 0:
         raise SlideHipError("%s failed with HIP status %d" % (what, status))
-
-
-def ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def stream_of(t=None):
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -18,7 +18,9 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
-from .engine import OP_ADVANCE_T, OP_UPDATE_FEAT, OP_UPDATE_POS, DenoiserEngine, SlideOp, make_op
+from .abi import (OP_ADVANCE_T, OP_ATTN_TAIL, OP_GEMM, OP_HEAD_UPDATE, OP_POINT_CHAIN, OP_PREP_POINTS, OP_SYNC, OP_UPDATE_FEAT,
+                  OP_UPDATE_POS, SlideHeadArgs, SlideOp, make_op)
+from .engine import DenoiserEngine
 
 F32 = np.float32
 
@@ -166,7 +168,6 @@ class _GraphedSampler:
         # fixed key points: the update kernel writes the feature columns the next step's point preparation would derive from
         # the new state (per-point table, concatenation columns), so SLIDE_OP_PREP_POINTS -- coordinates and neighbour tables,
         # constant over the chain -- runs once per chain in begin() instead of once per step (SLIDE_FUSE_PREP=0: per step)
-        from .engine import OP_PREP_POINTS
         self.fuse_prep = False
         if (fixed_xyz and update_op.kind == OP_UPDATE_FEAT and os.environ.get("SLIDE_FUSE_PREP", "1") != "0"
                 and e.ops[e._prep_idx].p[5] is None):  # (no chunk-major second copy of the table)
@@ -183,8 +184,7 @@ class _GraphedSampler:
         # the state update of 3264 elements in sequence, where the three launches spread them over 22 + 44 + 71 workgroups
         head = getattr(e, "head", None)
         if (head is not None and os.environ.get("SLIDE_HEAD_UPDATE", "0") != "0" and update_op.kind in (OP_UPDATE_POS, OP_UPDATE_FEAT)
-                and e.ops[head["idx"][0]].kind == 1 and e.ops[head["idx"][1]].kind == 1 and head["idx"][1] == e.eps_copy_idx - 1):
-            from .engine import OP_HEAD_UPDATE, SlideHeadArgs
+                and e.ops[head["idx"][0]].kind == OP_GEMM and e.ops[head["idx"][1]].kind == OP_GEMM and head["idx"][1] == e.eps_copy_idx - 1):
             h, u = SlideHeadArgs(), update_op
             h.X, h.W0, h.W1, h.v0, h.b1 = (head[k_].data_ptr() for k_ in ("X", "W0", "W1", "v0", "b1"))
             h.eps_out = None
@@ -208,8 +208,7 @@ class _GraphedSampler:
         # prediction (SLIDE_OP_POINT_CHAIN, csrc/point_chain.hip); the update launch follows as before.  SLIDE_POINT_CHAIN=0: four launches
         pch = getattr(e, "point_chain", None)
         chain_at = None
-        if pch is not None and not (set(pch["idx"]) & drop) and all(e.ops[i].kind == 1 for i in pch["idx"]):
-            from .engine import OP_POINT_CHAIN
+        if pch is not None and not (set(pch["idx"]) & drop) and all(e.ops[i].kind == OP_GEMM for i in pch["idx"]):
             c = e.point_chain_args()
             # OPT-IN (SLIDE_POINT_CHAIN_UPDATE=1): the feature DDPM's update in the same launch, its noise drawn in the shadow of the
             # chain's loads -- measured SLOWER (382.8 vs 389.8 shapes/s, three alternating pairs; the launch 18.7 -> 45.8 us): the
@@ -231,7 +230,6 @@ class _GraphedSampler:
             drop = drop | set(pch["idx"][1:])
         abl = os.environ.get("SLIDE_ABL_DROP")
         if abl:  # TIMING ablation (tools/ab/r05_ablate.sh): the launches whose kernel name contains one of the substrings are left out -- wrong results
-            from .engine import OP_ATTN_TAIL, OP_GEMM
             names = getattr(e, "kernel_names", {})
             lab = lambda i: names.get(i, "") + (" gemm16" if e.ops[i].kind == OP_GEMM and e.ops[i].i[0] == 16 * e.B else "") + \
                 (" tail" if e.ops[i].kind == OP_ATTN_TAIL else "")
@@ -268,8 +266,8 @@ class _GraphedSampler:
         e = self.engine
         L = lib()
         with torch.cuda.stream(self.stream):
-            s = ctypes.c_void_p(self.stream.cuda_stream)
-            s2 = ctypes.c_void_p(self.stream2.cuda_stream)
+            s = self.stream.cuda_stream
+            s2 = self.stream2.cuda_stream
             if not self.use_graph:
                 for _ in range(n_steps):
                     check(L.slide_run_ops2(self.step_ops, len(self.step_ops), s, s2), "slide_run_ops")
@@ -447,7 +445,6 @@ class JointSampler:
     def __init__(self, pos, feat):
         """pos may be None: the step graph then holds the feature plan alone (a further feature sub-batch of a
         SplitJointSampler whose position chain runs unsplit beside the first one)"""
-        from .engine import OP_SYNC
         self.pos, self.feat = pos, feat
         ops = []
         if pos is not None:
@@ -472,7 +469,7 @@ class JointSampler:
         if self.graph is not None:
             return
         with torch.cuda.stream(self.stream):
-            s, s2 = ctypes.c_void_p(self.stream.cuda_stream), ctypes.c_void_p(self.stream2.cuda_stream)
+            s, s2 = self.stream.cuda_stream, self.stream2.cuda_stream
             engines = [smp.engine for smp in (self.pos, self.feat) if smp is not None]
             keep = [(e.x.clone(), e.t_dev.clone()) for e in engines]
             check(L.slide_run_ops2(self.step_ops, len(self.step_ops), s, s2), "slide_run_ops2")
@@ -491,7 +488,7 @@ class JointSampler:
             self.graph = g
 
     def _launch(self):
-        check(lib().slide_graph_launch(self.graph, ctypes.c_void_p(self.stream.cuda_stream)), "graph_launch")
+        check(lib().slide_graph_launch(self.graph, self.stream.cuda_stream), "graph_launch")
 
     def _finish(self):
         self.stream2.wait_stream(self.stream)
@@ -520,10 +517,10 @@ class OwnGraphSampler:
     def _launch(self):
         smp = self.sampler
         if smp.use_graph:
-            check(lib().slide_graph_launch(smp.graph, ctypes.c_void_p(self.stream.cuda_stream)), "graph_launch")
+            check(lib().slide_graph_launch(smp.graph, self.stream.cuda_stream), "graph_launch")
         else:  # eager replay of the step plan (A/B against the graph form)
-            check(lib().slide_run_ops2(smp.step_ops, len(smp.step_ops), ctypes.c_void_p(self.stream.cuda_stream),
-                                       ctypes.c_void_p(smp.stream2.cuda_stream)), "slide_run_ops2")
+            check(lib().slide_run_ops2(smp.step_ops, len(smp.step_ops), self.stream.cuda_stream,
+                                       smp.stream2.cuda_stream), "slide_run_ops2")
 
     def _finish(self):
         pass
@@ -544,8 +541,8 @@ class ThreadedEagerSampler:
 
     def _issue(self, smp, n):
         torch.cuda.set_device(smp.device)  # HIP's current device is per host thread
-        return lib().slide_run_ops_repeat(smp.step_ops, len(smp.step_ops), ctypes.c_void_p(smp.stream.cuda_stream),
-                                          ctypes.c_void_p(smp.stream2.cuda_stream), int(n))
+        return lib().slide_run_ops_repeat(smp.step_ops, len(smp.step_ops), smp.stream.cuda_stream,
+                                          smp.stream2.cuda_stream, int(n))
 
     def advance(self, n_steps):
         if not self._warm:

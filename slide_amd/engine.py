@@ -16,113 +16,9 @@ import numpy as np
 import torch
 
 from ._lib import SlideHipError, check, lib
-
-EPI_RAW, EPI_NORM, EPI_STATS = 0, 1, 2
-F_PRE_RELU, F_POST_RELU, F_OUT_F32, F_RES_PAIR, F_RES_PAIR_NBR, F_OUT_FM = 1, 2, 4, 8, 16, 32
-# "split": the fp32 plan (float storage, same ops) with its contractions on the fp16 matrix pipe as two-term operand splits --
-# fp32-grade results (include/slide_engine.h: SLIDE_PREC_SPLIT)
-PREC = {"fp32": 0, "fp16": 1, "split": 2}
-(OP_GEMM, OP_PREP_POINTS, OP_ASSEMBLE_SA, OP_ASSEMBLE_FP, OP_FINALIZE_GN, OP_ATTN_COMBINE, OP_COPY_COLS, OP_TEMB,
- OP_COND, OP_UPDATE_POS, OP_UPDATE_FEAT, OP_ADVANCE_T) = range(1, 13)
-OP_SYNC = 14
-OP_ATTN_TAIL = 16
-OP_GEMM_GX, OP_PAIR_NORM, OP_SA_CHAIN, OP_BLOCK_BODY, OP_PAIR_FIRST, OP_GEMM_CHAIN, OP_HEAD_UPDATE, OP_GEMM_GX_DUAL, OP_SA_CHAIN_P = 17, 18, 19, 30, 31, 32, 33, 34, 35
-OP_PP_STAGE = 36
-OP_POINT_CHAIN = 37
-
-
-class SlideEpi(ctypes.Structure):
-    _fields_ = [("mode", ctypes.c_int32), ("flags", ctypes.c_int32), ("gs", ctypes.c_int32), ("n_norm", ctypes.c_int32),
-                ("inv_count", ctypes.c_float), ("stats_scale", ctypes.c_float),
-                ("out_ld", ctypes.c_int32), ("res_ld", ctypes.c_int32),
-                ("addvec_bs", ctypes.c_int32), ("stats_bs", ctypes.c_int32), ("pre_add_ld", ctypes.c_int32),
-                ("pre_add_shift", ctypes.c_int32), ("addvec_idx_stride", ctypes.c_int32), ("pad0", ctypes.c_int32),
-                ("bias", ctypes.c_void_p), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
-                ("addvec", ctypes.c_void_p), ("addvec_idx", ctypes.c_void_p), ("residual", ctypes.c_void_p),
-                ("pre_add", ctypes.c_void_p), ("out", ctypes.c_void_p),
-                ("stats_sum", ctypes.c_void_p), ("stats_sq", ctypes.c_void_p),
-                ("res_b", ctypes.c_void_p), ("res_vd", ctypes.c_void_p), ("res_vw", ctypes.c_void_p)]
-
-
-class SlideGnFin(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ("sum", "sq", "gid", "gstart", "gend", "gamma", "beta", "scale", "shift")] + [
-        ("inv_count", ctypes.c_float), ("C", ctypes.c_int32), ("bs", ctypes.c_int32), ("G", ctypes.c_int32)]
-
-
-class BodySlot(ctypes.Structure):  # csrc/block_body.hip
-    _fields_ = [("src", ctypes.c_void_p), ("chunk_stride", ctypes.c_int32), ("nrows", ctypes.c_int32),
-                ("kind", ctypes.c_int32), ("nvalid", ctypes.c_int32)]
-
-
-class BodyArgs(ctypes.Structure):  # csrc/block_body.hip (same field order: natural alignment on both sides)
-    _fields_ = [("slots", ctypes.c_void_p), ("n_slots", ctypes.c_int32),
-                ("ta", ctypes.c_void_p), ("tb", ctypes.c_void_p),
-                ("t_ld", ctypes.c_int32), ("off1", ctypes.c_int32), ("k1", ctypes.c_int32), ("offr", ctypes.c_int32),
-                ("offk", ctypes.c_int32), ("kk", ctypes.c_int32),
-                ("vv", ctypes.c_void_p), ("vbs", ctypes.c_int32), ("rv", ctypes.c_void_p),
-                ("nbr", ctypes.c_void_p), ("d2", ctypes.c_void_p), ("w", ctypes.c_void_p),
-                ("add0", ctypes.c_void_p), ("add0_idx", ctypes.c_void_p), ("add0_stride", ctypes.c_int32), ("add0_bs", ctypes.c_int32),
-                ("sc", ctypes.c_void_p), ("sh", ctypes.c_void_p), ("aff_bs", ctypes.c_int32),
-                ("P", ctypes.c_void_p), ("p_ld", ctypes.c_int32),
-                ("vec1", ctypes.c_void_p), ("n1", ctypes.c_int32), ("gs1", ctypes.c_int32), ("inv1", ctypes.c_float),
-                ("add1", ctypes.c_void_p), ("add1_bs", ctypes.c_int32),
-                ("vecm", ctypes.c_void_p), ("n_mo", ctypes.c_int32), ("gsm", ctypes.c_int32), ("invm", ctypes.c_float),
-                ("addm", ctypes.c_void_p), ("addm_bs", ctypes.c_int32),
-                ("vecu", ctypes.c_void_p), ("n_u", ctypes.c_int32), ("gsu", ctypes.c_int32), ("nnu", ctypes.c_int32), ("invu", ctypes.c_float),
-                ("vect", ctypes.c_void_p), ("n_out", ctypes.c_int32), ("gsv", ctypes.c_int32), ("nnv", ctypes.c_int32), ("invv", ctypes.c_float),
-                ("out", ctypes.c_void_p), ("out_ld", ctypes.c_int32), ("out2", ctypes.c_void_p), ("out2_ld", ctypes.c_int32), ("out2_n", ctypes.c_int32),
-                ("B", ctypes.c_int32), ("dbg", ctypes.c_void_p)]
-
-
-class SlideChainLayer(ctypes.Structure):  # include/slide_engine.h
-    _fields_ = [("X", ctypes.c_void_p), ("W", ctypes.c_void_p), ("epi", ctypes.c_void_p),
-                ("x_ld", ctypes.c_int32), ("k_pad", ctypes.c_int32), ("n_cob", ctypes.c_int32), ("pad", ctypes.c_int32)]
-
-
-class SlideHeadArgs(ctypes.Structure):  # include/slide_engine.h
-    _fields_ = [("X", ctypes.c_void_p), ("W0", ctypes.c_void_p), ("W1", ctypes.c_void_p), ("v0", ctypes.c_void_p),
-                ("b1", ctypes.c_void_p), ("eps_out", ctypes.c_void_p),
-                ("rows", ctypes.c_int32), ("x_ld", ctypes.c_int32), ("k0", ctypes.c_int32), ("n1c", ctypes.c_int32),
-                ("eps_ld", ctypes.c_int32),
-                ("kind", ctypes.c_int32), ("C", ctypes.c_int32), ("kdim", ctypes.c_int32), ("ldf", ctypes.c_int32),
-                ("half_out", ctypes.c_int32), ("n_copies", ctypes.c_int32),
-                ("clamp", ctypes.c_float), ("seed_lo", ctypes.c_uint32), ("seed_hi", ctypes.c_uint32),
-                ("x", ctypes.c_void_p), ("noise", ctypes.c_void_p), ("t_dev", ctypes.c_void_p),
-                ("keypoint", ctypes.c_void_p), ("t0", ctypes.c_void_p), ("t1", ctypes.c_void_p), ("t2", ctypes.c_void_p),
-                ("t3", ctypes.c_void_p), ("t4", ctypes.c_void_p), ("complete_x0", ctypes.c_void_p), ("kmask", ctypes.c_void_p),
-                ("feat0", ctypes.c_void_p), ("copies", ctypes.c_void_p)]
-
-
-class SlidePointChainArgs(ctypes.Structure):  # include/slide_engine.h
-    _fields_ = [("Z", ctypes.c_void_p), ("Wz", ctypes.c_void_p), ("W2", ctypes.c_void_p), ("W0", ctypes.c_void_p), ("W1", ctypes.c_void_p),
-                ("vz", ctypes.c_void_p), ("v2", ctypes.c_void_p), ("v0", ctypes.c_void_p), ("b1", ctypes.c_void_p),
-                ("tvec", ctypes.c_void_p), ("t_idx", ctypes.c_void_p), ("cvec", ctypes.c_void_p), ("X", ctypes.c_void_p),
-                ("eps", ctypes.c_void_p),
-                ("Wz_lo", ctypes.c_void_p), ("W2_lo", ctypes.c_void_p), ("W0_lo", ctypes.c_void_p), ("W1_lo", ctypes.c_void_p),
-                ("rows", ctypes.c_int32), ("z_ld", ctypes.c_int32), ("kz", ctypes.c_int32), ("x_ld", ctypes.c_int32),
-                ("k0", ctypes.c_int32), ("n1c", ctypes.c_int32), ("eps_ld", ctypes.c_int32), ("t_stride", ctypes.c_int32),
-                ("t_bs", ctypes.c_int32), ("c_bs", ctypes.c_int32), ("fuse_update", ctypes.c_int32), ("upd", SlideHeadArgs)]
-
-
-class SlideOp(ctypes.Structure):
-    _fields_ = [("kind", ctypes.c_int32), ("i", ctypes.c_int32 * 11), ("f", ctypes.c_float * 4),
-                ("p", ctypes.c_void_p * 14)]
-
-
-def ru(x, m=32):
-    return (x + m - 1) // m * m
-
-
-def make_op(kind, i=(), f=(), p=()):
-    o = SlideOp()
-    o.kind = kind
-    for k, v in enumerate(i):
-        o.i[k] = int(v)
-    for k, v in enumerate(f):
-        o.f[k] = float(v)
-    for k, v in enumerate(p):
-        o.p[k] = None if v is None else int(v)
-    return o
+# the C side of include/slide_engine.h -- every OP_* / EPI_* / F_* constant, PREC, the struct mirrors, make_op and ru -- is declared
+# in abi.py; all of it stays importable from this module
+from .abi import *  # noqa: F401,F403
 
 
 def gn_layout(C):
@@ -162,11 +58,6 @@ class _Arena:
         t = t.to(self.device)
         self.keep.append(t)
         return t
-
-
-class SlidePrepCopy(ctypes.Structure):
-    _fields_ = [("dst", ctypes.c_void_p), ("ld", ctypes.c_int32), ("kind", ctypes.c_int32), ("n", ctypes.c_int32),
-                ("pad", ctypes.c_int32)]
 
 
 class DenoiserEngine:
@@ -1836,16 +1727,13 @@ class DenoiserEngine:
         self._tail_of = {k_: remap[v] for k_, v in self._tail_of.items()}
 
     # ------------------------------------------------------------------ execution
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     def run(self, ops_array, n=None):
         if self.x.device.type != "cuda":
             raise SlideHipError("DenoiserEngine plans only run on a GPU; there is no CPU fallback")
         if getattr(self, "_side", None) is None:
             self._side = torch.cuda.Stream(device=self.x.device)
-        check(lib().slide_run_ops2(ops_array, len(ops_array) if n is None else n, self._stream(),
-                                   ctypes.c_void_p(self._side.cuda_stream)), "slide_run_ops2")
+        check(lib().slide_run_ops2(ops_array, len(ops_array) if n is None else n, stream_of(),
+                                   self._side.cuda_stream), "slide_run_ops2")
 
     def prepare(self):
         """sampler mode: fill the per-timestep t-embedding table (once)"""

@@ -19,14 +19,16 @@ import numpy as np
 import torch
 
 from .._lib import LIB_EXP_PATH, SlideHipError, _load, check
+from ..abi import OP_TEMB, SlideOp
+from ..engine import DenoiserEngine
 
 
 def lib():
     """the resident kernel only exists in the EXPERIMENTS build of the library"""
     return _load(LIB_EXP_PATH)
 
-from ..engine import DenoiserEngine
 
+# include/experiments/slide_resident.h (SLIDE_R_* ...); tests/test_abi_mirror.py compares these and the four structs below with it
 R_PREP, R_ASSEMBLE, R_GEMM, R_FINALIZE, R_AFFINE, R_TAIL, R_ZFILL = range(1, 8)
 RS_RAW, RS_NORM, RS_STATS = 0, 1, 2
 RF_PRE_RELU, RF_POST_RELU, RF_OUT_F32 = 1, 2, 4
@@ -456,8 +458,8 @@ class ResidentPlan:
         return a
 
 
-def _run(a, stream):
-    check(lib().slide_resident_run(ctypes.byref(a), ctypes.c_void_p(stream.cuda_stream)), "slide_resident_run")
+def _launch(a, stream):
+    check(lib().slide_resident_run(ctypes.byref(a), stream.cuda_stream), "slide_resident_run")
 
 
 class ResidentDenoiser:
@@ -476,11 +478,10 @@ class ResidentDenoiser:
         e.x.copy_(torch.as_tensor(x).to(e.device, torch.float32).reshape(e.x.shape))
         e.ts.copy_(torch.as_tensor(ts).to(e.device, torch.float32).reshape(e.B))
         e.set_label(label)
-        from ..engine import OP_TEMB, SlideOp
         temb = [o for o in e.ops if o.kind == OP_TEMB]
         e.run((SlideOp * 1)(temb[0]))
         d = torch.zeros(e.B, self.plan.lds_bytes, dtype=torch.uint8, device=e.device) if dbg else None
-        _run(self.plan.args(1, e.x, eps_out=self.eps, per_sample_t=True, dbg=d), torch.cuda.current_stream())
+        _launch(self.plan.args(1, e.x, eps_out=self.eps, per_sample_t=True, dbg=d), torch.cuda.current_stream())
         return (self.eps.clone(), d) if dbg else self.eps.clone()
 
 
@@ -526,8 +527,8 @@ class ResidentPositionSampler:
         if n_steps <= 0:
             return
         with torch.cuda.stream(self.stream):
-            _run(self.plan.args(n_steps, self.engine.x, t_dev=self.engine.t_dev, tabs=self.tabs, noise=self.noise, seed=self.seed),
-                 self.stream)
+            _launch(self.plan.args(n_steps, self.engine.x, t_dev=self.engine.t_dev, tabs=self.tabs, noise=self.noise, seed=self.seed),
+                    self.stream)
 
     def state(self):
         with torch.cuda.stream(self.stream):

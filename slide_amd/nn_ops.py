@@ -3,27 +3,15 @@
 (the parity mode every module-level test uses).  `SLIDE_MODULE_PREC=fp16` switches the GEMM operands (weights, the
 transposed activation copy) to fp16 with fp32 accumulation and fp32 outputs -- the throughput mode of the encode / decode
 paths.  Inference only.  The fused, layout-optimised path for the DDPM configs is slide_amd.engine.DenoiserEngine."""
-import ctypes
 import os
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from ._lib import check, lib
-from .engine import EPI_RAW, F_OUT_F32, OP_GEMM, SlideEpi, SlideOp, make_op, ru
-
-OP_GROUPNORM_NCHW = 13
-OP_TRANSPOSE = 15
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _run(op):
-    arr = (SlideOp * 1)(op)
-    check(lib().slide_run_ops(arr, 1, _stream()), "slide_run_ops")
+from .abi import EPI_RAW, F_OUT_F32, OP_GROUPNORM_NCHW, OP_TRANSPOSE, SlideEpi, make_op, ru
+from .abi import run_op as _run
+from .rows import module_gemm_op
 
 
 class _GemmPlan:
@@ -54,10 +42,7 @@ class _GemmPlan:
             e.bias = vec.data_ptr() + 4 * 32 * j
             e.out = self.y.data_ptr() + 4 * 32 * j
         self.epi = torch.from_numpy(np.frombuffer(bytes(epis), dtype=np.uint8).copy()).to(device)
-        ntr = (rows + 255) // 256
-        cbw = 4 if (self.half and n_cob >= 4 and ntr * ((n_cob + 3) // 4) >= 256 and os.environ.get("SLIDE_MODULE_CBW4", "0") != "0") else 2
-        self.op = make_op(OP_GEMM, i=(rows, self.kp, self.kp, n_cob, 8, 0, int(self.half), cbw, int(self.half), 0),
-                          p=(self.x.data_ptr(), self.W.data_ptr(), self.epi.data_ptr(), None, None))
+        self.op = module_gemm_op(rows, self.kp, n_cob, self.half, p=(self.x.data_ptr(), self.W.data_ptr(), self.epi.data_ptr()))
 
     def __call__(self, x2d):
         self.x[:, : self.I].copy_(x2d)

@@ -9,32 +9,21 @@ the t- and class-embedding adds / the residual run in place in one pass, and the
 Reference-layout tensors exist only at module boundaries (`from_ncx` / `to_ncx`).
 
 Everything here launches kernels of libslide_hip.so (rows_ops.hip + the engine GEMM); there is no CPU fallback."""
-import ctypes
 import os
 
 import numpy as np
 import torch
 
-from ._lib import check, lib
-from .engine import EPI_RAW, EPI_STATS, F_OUT_F32, F_PRE_RELU, OP_GEMM, SlideEpi, SlideOp, make_op, ru
-
-OP_COPY_COLS = 7
-OP_ROWS_FROM_NCX, OP_ROWS_TO_NCX, OP_ROWS_GROUP, OP_ROWS_GN, OP_ROWS_CONCAT_QK, OP_ROWS_ATTN, OP_ROWS_POOL = 20, 21, 22, 23, 24, 25, 26
-OP_ROWS_GN_JOINT = 27
-OP_GEMM_ATTEND = 38
-OP_ROWS_PAIR_EXPAND = 39
-GROUP_FP, GROUP_ABS, GROUP_CENTER, GROUP_NO_XYZ, GROUP_IDX32 = 1, 2, 4, 8, 16
-POOL_MAX, POOL_AVG, POOL_MAX_AVG = 0, 1, 2
-GN_PRE_RELU, GN_POST_RELU, GN_STATS_ONLY, GN_APPLY_ONLY = 1, 2, 4, 8
+from .abi import (EPI_RAW, EPI_STATS, F_OUT_F32, F_PRE_RELU, GN_APPLY_ONLY, GN_POST_RELU, GN_PRE_RELU, GN_STATS_ONLY,  # noqa: F401
+                  GROUP_ABS, GROUP_CENTER, GROUP_FP, GROUP_IDX32, GROUP_NO_XYZ, OP_COPY_COLS, OP_GEMM, OP_GEMM_ATTEND,
+                  OP_ROWS_ATTN, OP_ROWS_CONCAT_QK, OP_ROWS_FROM_NCX, OP_ROWS_GN, OP_ROWS_GN_JOINT, OP_ROWS_GROUP,
+                  OP_ROWS_PAIR_EXPAND, OP_ROWS_POOL, OP_ROWS_TO_NCX, POOL_AVG, POOL_MAX, POOL_MAX_AVG, SlideEpi, SlideOp,
+                  make_op, ru)
+from .abi import run_op as _run
 
 
 def half_mode():
     return os.environ.get("SLIDE_MODULE_PREC", "fp32") == "fp16"
-
-
-def _run(op):
-    arr = (SlideOp * 1)(op)
-    check(lib().slide_run_ops(arr, 1, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "slide_run_ops")
 
 
 def _rop(kind, half, i, p):
@@ -205,6 +194,15 @@ class _PinnedUploader:
 _uploader = _PinnedUploader()
 
 
+def module_gemm_op(rows, kp, n_cob, half, in_bs=0, f=(), p=()):
+    """the SLIDE_OP_GEMM of the module-level path: x [rows][kp] against n_cob 32-channel blocks of a row-major weight on 256-row tiles,
+    fp32 or (half) fp16 operands on the LDS-DMA ring kernels; four-block column tiles only on request (SLIDE_MODULE_CBW4) and when
+    they still give 256 workgroups"""
+    ntr = (rows + 255) // 256
+    cbw = 4 if (half and n_cob >= 4 and ntr * ((n_cob + 3) // 4) >= 256 and os.environ.get("SLIDE_MODULE_CBW4", "0") != "0") else 2
+    return make_op(OP_GEMM, i=(rows, kp, kp, n_cob, 8, in_bs, int(half), cbw, int(half), 0), f=f, p=p)
+
+
 class _ConvPlan:
     """packed weight + bias of one 1x1 convolution / linear for the row-major GEMM: y[rows, O] = x[rows, I] @ W^T + b"""
 
@@ -278,9 +276,6 @@ class _ConvPlan:
         st = None
         if stats is not None and x.S % 256 == 0 and fused_stats():
             st = (torch.empty(rows // 256, self.op_, device=out.device), torch.empty(rows // 256, self.op_, device=out.device))
-        n_cob = self.op_ // 32
-        ntr = (rows + 255) // 256
-        cbw = 4 if (self.half and n_cob >= 4 and ntr * ((n_cob + 3) // 4) >= 256 and os.environ.get("SLIDE_MODULE_CBW4", "0") != "0") else 2
         sc = sh = add = None
         f = (0.0, 0.0, 0.0, 0.0)
         in_bs = 0
@@ -290,9 +285,9 @@ class _ConvPlan:
             add = None if addvec is None else addvec.data_ptr()
             f = (0.0, float(x.S // 256), float(addvec.shape[1]) if addvec is not None else 0.0,
                  float(2 * (addvec.shape[1] if addvec is not None else 0) + int(relu)))
-        _run(make_op(OP_GEMM, i=(rows, self.kp, self.kp, n_cob, 8, in_bs, int(self.half), cbw, int(self.half), 0), f=f,
-                     p=(x.data.data_ptr(), self.W.data_ptr(), self.epi_ptr(out, st, stats == "relu", pa, out_f32), sc, sh,
-                        None, None, None, None, None, None, add)))
+        _run(module_gemm_op(rows, self.kp, self.op_ // 32, self.half, in_bs=in_bs, f=f,
+                            p=(x.data.data_ptr(), self.W.data_ptr(), self.epi_ptr(out, st, stats == "relu", pa, out_f32), sc, sh,
+                               None, None, None, None, None, None, add)))
         return Rows(out, x.B, x.S, self.O, stats=None if st is None else (st[0], st[1], stats == "relu"))
 
 

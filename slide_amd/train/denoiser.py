@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from .. import _ext, model_spec
-from ..rows import GROUP_ABS, GROUP_CENTER, GROUP_FP
+from ..abi import GROUP_ABS, GROUP_CENTER, GROUP_FP
 from . import functions as F
 
 

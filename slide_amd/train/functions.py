@@ -12,20 +12,9 @@ from torch.autograd.function import once_differentiable
 
 from .. import _ext
 from .._lib import check, lib
-from ..engine import EPI_RAW, OP_GEMM, SlideEpi, make_op, ru
-from ..rows import (GN_POST_RELU, GN_PRE_RELU, GROUP_ABS, GROUP_CENTER, GROUP_FP, GROUP_IDX32, GROUP_NO_XYZ, OP_ROWS_ATTN,
-                    OP_ROWS_CONCAT_QK, OP_ROWS_GN, OP_ROWS_GROUP, _rop, _run)
-
-PREC_SPLIT = 2
-_c = ctypes.c_void_p
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return None if t is None else _c(t.data_ptr())
+from ..abi import (EPI_RAW, GN_POST_RELU, GN_PRE_RELU, GROUP_ABS, GROUP_CENTER, GROUP_FP, GROUP_IDX32, GROUP_NO_XYZ, OP_GEMM,
+                   OP_ROWS_ATTN, OP_ROWS_CONCAT_QK, OP_ROWS_GN, OP_ROWS_GROUP, PREC_SPLIT, SlideEpi, make_op, ptr, ru, stream_of)
+from ..rows import _rop, _run
 
 
 def _chk(x):
@@ -114,7 +103,7 @@ def col_sums(x):
     (semaphore + staging buffer) returned garbage inside replayed HIP graphs (tools/debug_train_nan4.py)."""
     rows, ld = x.shape
     buf = torch.empty(1025 if rows >= 128 else 1, ld, device=x.device, dtype=torch.float32)
-    check(lib().slide_col_sums(ctypes.c_longlong(rows), ld, _p(x), _p(buf), _c(buf.data_ptr() + 4 * ld) if rows >= 128 else None, _stream()),
+    check(lib().slide_col_sums(rows, ld, ptr(x), ptr(buf), buf.data_ptr() + 4 * ld if rows >= 128 else None, stream_of()),
           "slide_col_sums")
     return buf[0]
 
@@ -203,8 +192,8 @@ class GroupNormRows(torch.autograd.Function):
             dg, db = torch.empty(B, ld, device=x.device), torch.empty(B, ld, device=x.device)
             scratch = torch.empty(B * (64 * ld * 2 + 128), device=x.device, dtype=torch.float32)
         if x.shape[0]:
-            check(lib().slide_gn_rows_bwd(B, S, ld, G, n_norm, flags, _p(x), _p(gam), _p(bet), _p(mr), _p(dy), _p(dx), _p(dg), _p(db),
-                                          _p(scratch), _stream()), "slide_gn_rows_bwd")
+            check(lib().slide_gn_rows_bwd(B, S, ld, G, n_norm, flags, ptr(x), ptr(gam), ptr(bet), ptr(mr), ptr(dy), ptr(dx), ptr(dg), ptr(db),
+                                          ptr(scratch), stream_of()), "slide_gn_rows_bwd")
         elif n_norm:
             dg.zero_(), db.zero_()
         return (dx, None if dg is None else col_sums(dg)[:n_norm], None if db is None else col_sums(db)[:n_norm], None, None, None, None, None)
@@ -258,16 +247,16 @@ class GroupRows(torch.autograd.Function):
         dfeat = dxyz = dnew = None
         if ldf and ctx.needs_input_grad[0]:
             dfeat = torch.zeros(B * N, ldf, device=dout.device, dtype=torch.float32)
-            check(lib().slide_group_rows_bwd(B, N, npnt, K, C, ldf, ldg, _p(idx if idx64 is None else idx64), _p(counts), _p(dout), _p(dfeat),
-                                             _stream()), "slide_group_rows_bwd")
+            check(lib().slide_group_rows_bwd(B, N, npnt, K, C, ldf, ldg, ptr(idx if idx64 is None else idx64), ptr(counts), ptr(dout), ptr(dfeat),
+                                             stream_of()), "slide_group_rows_bwd")
         if need_coord:
             xyz, new_xyz, d2 = ctx.saved_tensors[3:]
             if ctx.needs_input_grad[1]:
                 dxyz = torch.zeros(B, N, 3, device=dout.device, dtype=torch.float32)  # (accumulated with atomics)
             if ctx.needs_input_grad[2]:
                 dnew = torch.empty(B, npnt, 3, device=dout.device, dtype=torch.float32)  # (written in full)
-            check(lib().slide_group_rows_coord_bwd(B, N, npnt, K, C, ldg, flags, _p(xyz), _p(new_xyz), _p(idx), _p(d2), _p(counts), _p(dout),
-                                                   _p(dxyz), _p(dnew), _stream()), "slide_group_rows_coord_bwd")
+            check(lib().slide_group_rows_coord_bwd(B, N, npnt, K, C, ldg, flags, ptr(xyz), ptr(new_xyz), ptr(idx), ptr(d2), ptr(counts), ptr(dout),
+                                                   ptr(dxyz), ptr(dnew), stream_of()), "slide_group_rows_coord_bwd")
         return dfeat, dxyz, dnew, None, None, None, None, None
 
 
@@ -293,7 +282,7 @@ class ConcatQK(torch.autograd.Function):
         pts = out.shape[0] // K
         dq = torch.zeros(pts, ldq, device=out.device, dtype=torch.float32)
         dk = torch.zeros(out.shape[0], ldk, device=out.device, dtype=torch.float32)
-        check(lib().slide_concat_qk_bwd(ctypes.c_longlong(pts), K, C1, ldq, C2, ldk, out.shape[1], _p(out), _p(dout), _p(dq), _p(dk), _stream()),
+        check(lib().slide_concat_qk_bwd(pts, K, C1, ldq, C2, ldk, out.shape[1], ptr(out), ptr(dout), ptr(dq), ptr(dk), stream_of()),
               "slide_concat_qk_bwd")
         return dq, dk, None, None, None
 
@@ -320,8 +309,8 @@ class AttendRows(torch.autograd.Function):
         dout = dout.contiguous()
         pts = scores.shape[0] // K
         ds, dv = torch.zeros_like(scores), torch.zeros_like(values)
-        check(lib().slide_attn_rows_bwd(ctypes.c_longlong(pts), K, C, scores.shape[1], values.shape[1], ldo, _p(scores), _p(values), None,
-                                        _p(dout), _p(ds), _p(dv), _stream()), "slide_attn_rows_bwd")
+        check(lib().slide_attn_rows_bwd(pts, K, C, scores.shape[1], values.shape[1], ldo, ptr(scores), ptr(values), None,
+                                        ptr(dout), ptr(ds), ptr(dv), stream_of()), "slide_attn_rows_bwd")
         return ds, dv, None, None
 
 

@@ -6,7 +6,7 @@ before, and the Chamfer gradient reaches that level through these terms.  No gra
 import torch
 
 from .. import _ext
-from ..rows import GROUP_ABS, GROUP_CENTER, GROUP_FP
+from ..abi import GROUP_ABS, GROUP_CENTER, GROUP_FP
 from .functions import group_rows
 
 

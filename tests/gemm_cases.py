@@ -38,6 +38,8 @@ import zlib
 
 import numpy as np
 
+from slide_amd.abi import ru  # noqa: F401  (used here and re-exported to the test modules)
+
 U = 2.0 ** -24
 C_ACC = 2.0 ** -18
 EPS = 1e-5
@@ -50,10 +52,6 @@ def r16(a):
 
 def r32(a):
     return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
-
-
-def ru(x, m=32):
-    return (x + m - 1) // m * m
 
 
 def _c(name, prec, npxl, B, K, N, mode, kernel, dist="normal", **kw):

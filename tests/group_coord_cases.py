@@ -37,13 +37,15 @@ import functools
 import numpy as np
 import torch
 
+from slide_amd import abi
+
 U = 2.0 ** -24
 FP, ABS, CENTER, NO_XYZ, IDX32 = 1, 2, 4, 8, 16
 MUTANTS = ("no_w_coupling", "no_factor_2", "centre_rel_sign", "no_g_d2", "counts_ignored")
 
 
 def ru(c):
-    return max(32, (c + 31) // 32 * 32)
+    return max(32, abi.ru(c))  # (a row has at least one 32-column block)
 
 
 def ncoord(flags):

@@ -67,6 +67,8 @@ import zlib
 
 import numpy as np
 
+from slide_amd.abi import ru  # noqa: F401  (used here and re-exported to the test modules)
+
 U = 2.0 ** -24
 EPS = 1e-5
 E_EXP = 2.0  # expf: 1 ulp = 2 u
@@ -83,10 +85,6 @@ def r16(a):
 
 def r32(a):
     return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
-
-
-def ru(x, m=32):
-    return (x + m - 1) // m * m
 
 
 def T(c, a):

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import NoiseStream, golden_spec, load_golden
+from slide_amd import abi
 from slide_amd.synth import synth_state_dict
 
 pytestmark = pytest.mark.gpu
@@ -460,7 +461,7 @@ def test_point_preparation_folded_into_the_update(gpu_device, monkeypatch, prec)
         monkeypatch.setenv("SLIDE_FUSE_PREP", fuse)
         smp = FeatureSampler(hp, sd, size[0], gpu_device, cfg, prec=prec, seed=77, use_graph=False)
         assert smp.fuse_prep == (fuse == "1")
-        assert sum(1 for o in smp.step_ops if o.kind == 2) == (0 if fuse == "1" else 1)  # SLIDE_OP_PREP_POINTS
+        assert sum(1 for o in smp.step_ops if o.kind == abi.OP_PREP_POINTS) == (0 if fuse == "1" else 1)  # SLIDE_OP_PREP_POINTS
         a_ = smp.sample(g["label"], g["keypoint"], xa, t_start=40, n_steps=12).cpu().numpy()
         b_ = smp.sample(g["label"], kp2, xb, t_start=999, n_steps=7).cpu().numpy()  # a second chain, other key points
         out[fuse] = (a_, b_)
@@ -488,7 +489,7 @@ def test_head_and_update_as_one_launch(gpu_device, exp_lib, monkeypatch):
         ps = PositionSampler(hpp, sdp, size[0], gpu_device, _pos_cfg(), prec="fp16", seed=9, use_graph=False)
         for smp in (fs, ps):
             kinds = [o.kind for o in smp.step_ops]
-            assert (33 in kinds) == (fuse == "1") and ((10 in kinds) or (11 in kinds)) == (fuse == "0")
+            assert (abi.OP_HEAD_UPDATE in kinds) == (fuse == "1") and ((abi.OP_UPDATE_POS in kinds) or (abi.OP_UPDATE_FEAT in kinds)) == (fuse == "0")
         out[fuse] = (fs.sample(g["label"], g["keypoint"], xf, t_start=60, n_steps=10).cpu().numpy(),
                      ps.sample(g["label"], xp, t_start=60, n_steps=10).cpu().numpy())
     for a_, b_ in zip(out["1"], out["0"]):
@@ -522,7 +523,7 @@ def test_point_chain_launch_matches_its_four_layers(gpu_device, monkeypatch):
             monkeypatch.setenv("SLIDE_POINT_CHAIN_UPDATE", upd)
             fs = FeatureSampler(hpf, sdf, B, gpu_device, cfg, prec="fp16", seed=9, use_graph=False)
             kinds = [o.kind for o in fs.step_ops]
-            assert (37 in kinds) == (on == "1") and (11 in kinds) == (tag != "fused"), kinds  # 11: SLIDE_OP_UPDATE_FEAT
+            assert (abi.OP_POINT_CHAIN in kinds) == (on == "1") and (abi.OP_UPDATE_FEAT in kinds) == (tag != "fused"), kinds
             nl[tag] = len(kinds)
             x1 = fs.sample(lab, kp, xf, t_start=60, n_steps=1)
             eps[tag] = fs.engine.eps_pad.float().cpu().numpy().copy()
@@ -797,14 +798,14 @@ def test_x_stationary_kernel_bit_identical(gpu_device, exp_lib, monkeypatch):
         x, ts, lab = g["x_mixed"], g["ts_mixed"], g["label_mixed"]
         monkeypatch.setenv("SLIDE_XS", "")  # ring kernels only
         e0 = DenoiserEngine(hp, sd, x.shape[0], gpu_device, prec="fp16")
-        assert not any(o.kind == 1 and o.p[10] for o in e0.ops)
+        assert not any(o.kind == abi.OP_GEMM and o.p[10] for o in e0.ops)
         ref = e0.forward(x, ts, lab).cpu().numpy()
         for mode, cbw, occ in (("auto", "2", ""), ("7,8", "2", ""), ("7,8", "4", "1"), ("8", "2", "2")):
             monkeypatch.setenv("SLIDE_XS", mode)
             monkeypatch.setenv("SLIDE_XS_CBW", cbw)
             monkeypatch.setenv("SLIDE_XS_OCC", occ) if occ else monkeypatch.delenv("SLIDE_XS_OCC", raising=False)
             e = DenoiserEngine(hp, sd, x.shape[0], gpu_device, prec="fp16")
-            assert any(o.kind == 1 and o.p[10] for o in e.ops)
+            assert any(o.kind == abi.OP_GEMM and o.p[10] for o in e.ops)
             got = e.forward(x, ts, lab).cpu().numpy()
             assert np.array_equal(got, ref), (name, mode, cbw, occ, float(np.abs(got - ref).max()))
 
@@ -828,13 +829,13 @@ def test_fragment_major_layout_bit_identical(gpu_device, monkeypatch):
                 xb, tb, lb = np.concatenate([x] * rep)[:B], np.concatenate([ts] * rep)[:B], np.concatenate([lab] * rep)[:B]
                 monkeypatch.setenv("SLIDE_FM", "0")
                 e0 = DenoiserEngine(hp, sd, B, gpu_device, prec="fp16")
-                assert not e0._fm and not any(o.kind == 16 and (int(o.f[1]) & 16) for o in e0.ops)
+                assert not e0._fm and not any(o.kind == abi.OP_ATTN_TAIL and (int(o.f[1]) & abi.TAIL_FM) for o in e0.ops)
                 ref = e0.forward(xb, tb, lb).cpu().numpy()
                 monkeypatch.setenv("SLIDE_FM", "1")
                 e1 = DenoiserEngine(hp, sd, B, gpu_device, prec="fp16")
-                tails = [o for o in e1.ops if o.kind == 16]
+                tails = [o for o in e1.ops if o.kind == abi.OP_ATTN_TAIL]
                 # (without the SA chain an SA block's rest_mlp is a ring GEMM over a stored h2: that block stays chunk-major)
-                nfm = sum(1 for o in tails if int(o.f[1]) & 16)
+                nfm = sum(1 for o in tails if int(o.f[1]) & abi.TAIL_FM)
                 # (the position net's narrow blocks are outside the layout's conditions -- _tail_fm: its plan must simply not change)
                 assert nfm == (0 if name == "pos" else 2 if "SLIDE_SA_CHAIN" in knobs else 4) and bool(e1._fm) == (nfm > 0), (name, knobs, B, nfm)
                 got = e1.forward(xb, tb, lb).cpu().numpy()
@@ -862,15 +863,15 @@ def test_chunk_major_layout_bit_identical(gpu_device, exp_lib, monkeypatch):
             monkeypatch.setenv("SLIDE_MERGE_Q", "0")  # (the reference plan is also the one-launch-per-query-GEMM plan
             monkeypatch.setenv("SLIDE_FOLD_COPIES", "0")  # with separate COPY launches for the concatenation columns)
             e0 = DenoiserEngine(hp, sd, x.shape[0], gpu_device, prec="fp16")
-            n_copy0 = sum(1 for o in e0.ops if o.kind == 7)
+            n_copy0 = sum(1 for o in e0.ops if o.kind == abi.OP_COPY_COLS)
             monkeypatch.setenv("SLIDE_MERGE_Q", knobs.get("SLIDE_MERGE_Q", "1"))
             monkeypatch.setenv("SLIDE_FOLD_COPIES", "1")
-            assert not e0._cm and not any(o.kind == 1 and (o.i[8] & 2) for o in e0.ops)
+            assert not e0._cm and not any(o.kind == abi.OP_GEMM and (o.i[8] & abi.GEMM_W_CM) for o in e0.ops)
             ref = e0.forward(x, ts, lab).cpu().numpy()
             monkeypatch.setenv("SLIDE_CM", "1")
             e1 = DenoiserEngine(hp, sd, x.shape[0], gpu_device, prec="fp16")
-            assert e1._cm and any(o.kind == 1 and (o.i[8] & 2) for o in e1.ops)
-            assert sum(1 for o in e1.ops if o.kind == 7) <= n_copy0 - 4  # skip-feature and xyz columns come from their producers
+            assert e1._cm and any(o.kind == abi.OP_GEMM and (o.i[8] & abi.GEMM_W_CM) for o in e1.ops)
+            assert sum(1 for o in e1.ops if o.kind == abi.OP_COPY_COLS) <= n_copy0 - 4  # skip-feature and xyz columns come from their producers
             got = e1.forward(x, ts, lab).cpu().numpy()
             assert np.array_equal(got, ref), (name, knobs, float(np.abs(got - ref).max()))
             for k_ in knobs:
@@ -901,13 +902,13 @@ def test_pair_decomposition_plan_variants(gpu_device, exp_lib, monkeypatch):
             e = DenoiserEngine(hp, sd, x.shape[0], gpu_device, prec="fp16")
             kinds = {o.kind for o in e.ops}
             if tag == "round2":
-                assert not kinds & {17, 18, 19, 30}
+                assert not kinds & {abi.OP_GEMM_GX, abi.OP_PAIR_NORM, abi.OP_SA_CHAIN, abi.OP_BLOCK_BODY}
             elif tag in ("pair_norm_v2", "two_launch_tables"):
-                assert 18 in kinds and 31 not in kinds  # SLIDE_OP_PAIR_NORM after a 16-row GEMM
+                assert abi.OP_PAIR_NORM in kinds and abi.OP_PAIR_FIRST not in kinds  # SLIDE_OP_PAIR_NORM after a 16-row GEMM
             else:
-                assert 31 in kinds and 18 not in kinds  # SLIDE_OP_PAIR_FIRST: GEMM + table pass in one launch
-            assert (32 in kinds) == ("gemm_chain" in tag)  # SLIDE_OP_GEMM_CHAIN (opt-in): per-point layer chains, one launch each
-            assert (30 in kinds) == (tag == "block_body" and name == "feat")  # SLIDE_OP_BLOCK_BODY (opt-in since round 5): FP0 of the feature net
+                assert abi.OP_PAIR_FIRST in kinds and abi.OP_PAIR_NORM not in kinds  # SLIDE_OP_PAIR_FIRST: GEMM + table pass in one launch
+            assert (abi.OP_GEMM_CHAIN in kinds) == ("gemm_chain" in tag)  # SLIDE_OP_GEMM_CHAIN (opt-in): per-point layer chains, one launch each
+            assert (abi.OP_BLOCK_BODY in kinds) == (tag == "block_body" and name == "feat")  # SLIDE_OP_BLOCK_BODY (opt-in since round 5): FP0 of the feature net
             outs[tag] = e.forward(x, ts, lab).cpu().numpy().astype(np.float64)
             for k_ in knobs:
                 monkeypatch.delenv(k_)
@@ -944,9 +945,9 @@ def test_split_pair_decomposition_plan_variants(gpu_device, exp_lib, monkeypatch
                 monkeypatch.setenv(k_, v_)
             e = DenoiserEngine(hp, sd, x.shape[0], gpu_device, prec="split")
             kinds = [o.kind for o in e.ops]
-            assert (17 in kinds or 34 in kinds) == (tag != "round4_plan")   # SLIDE_OP_GEMM_GX / _DUAL
-            assert (6 in kinds) == (tag in ("round4_plan", "three_launch_tail"))  # SLIDE_OP_ATTN_COMBINE
-            assert (36 in kinds) == (tag == "per_point_stage")              # SLIDE_OP_PP_STAGE
+            assert (abi.OP_GEMM_GX in kinds or abi.OP_GEMM_GX_DUAL in kinds) == (tag != "round4_plan")   # SLIDE_OP_GEMM_GX / _DUAL
+            assert (abi.OP_ATTN_COMBINE in kinds) == (tag in ("round4_plan", "three_launch_tail"))  # SLIDE_OP_ATTN_COMBINE
+            assert (abi.OP_PP_STAGE in kinds) == (tag == "per_point_stage")              # SLIDE_OP_PP_STAGE
             if tag == "default" and name == "pos":
                 assert len(kinds) <= 30, len(kinds)  # (round 4: 49 launches + the t-embedding launch of the forward API)
             outs[tag] = e.forward(x, ts, lab).cpu().numpy().astype(np.float64)

@@ -24,7 +24,7 @@ os.environ["SLIDE_HIP_LIB"] = LIBT
 import torch
 from slide_amd import configs, model_spec
 from slide_amd._lib import check, lib
-from slide_amd.engine import SlideOp
+from slide_amd.abi import OP_ATTN_TAIL, OP_BLOCK_BODY, OP_GEMM_GX, OP_SA_CHAIN, SlideOp
 from slide_amd.diffusion import FeatureSampler, PositionSampler
 from slide_amd.synth import synth_keypoints, synth_state_dict
 which, B = sys.argv[1], int(sys.argv[2])
@@ -52,7 +52,7 @@ with torch.cuda.stream(s.stream):
         nwg = 16384
         dbg = torch.zeros(nwg * 16, dtype=torch.int64, device=dev)
         slot = {1: 5, 17: 12, 19: 12, 16: 8, 30: 1, 31: 13}.get(op.kind)
-        if op.kind == 17 and int(op.f[0]) == 3:  # split generated-X GEMM (gemm_gxs.hip): p[12] / p[13] carry a chained layer
+        if op.kind == OP_GEMM_GX and int(op.f[0]) == 3:  # split generated-X GEMM (gemm_gxs.hip): p[12] / p[13] carry a chained layer
             slot = None if op.p[12] else 13
         if slot is None:
             print("op %d: kind %d carries no stamps" % (idx, op.kind)); continue
@@ -67,17 +67,17 @@ with torch.cuda.stream(s.stream):
             print("op %d kind %d: no stamps (kernel variant without instrumentation)" % (idx, op.kind)); continue
         t0 = t[:, 0].min()
         t = (t - t0) / 100.0
-        seq = [0, 7, 1, 2, 3, 4, 5, 6] if op.kind == 17 else [0, 1, 2, 3, 4, 5, 6]
+        seq = [0, 7, 1, 2, 3, 4, 5, 6] if op.kind == OP_GEMM_GX else [0, 1, 2, 3, 4, 5, 6]
         names = {0: "start", 7: "tables", 1: "primed", 2: "kloop", 3: "stats", 4: "barrier", 5: "stored", 6: "retired"}
-        if op.kind == 16:  # eight-wave attention tail: 1 first DMA issued | 2 landed | 3 scores K loop | 4 values K loop | 5 statistics | 6 softmax + stores | 7 retired
+        if op.kind == OP_ATTN_TAIL:  # eight-wave attention tail: 1 first DMA issued | 2 landed | 3 scores K loop | 4 values K loop | 5 statistics | 6 softmax + stores | 7 retired
             seq = [0, 1, 2, 3, 4, 5, 6, 7]
             names = {1: "prologue", 2: "first_stage", 3: "kloop_s", 4: "kloop_v", 5: "stats", 6: "softmax", 7: "retired"}
             if os.environ.get("SLIDE_TAIL8", "0") == "0":  # register-X tail: 1 pipeline primed | 2 first RXD chunks | 3 values K loop | 4 scores K loop | 5 drained + barrier | 6 epilogue | 7 retired
                 names = {1: "primed", 2: "first4", 3: "kloop_v", 4: "kloop_s", 5: "drain", 6: "epilogue", 7: "retired"}
-        if op.kind == 30:  # block body: 1 prologue | 2 h2 | 3 mo | 4 u | 5 tail | 6 retired
+        if op.kind == OP_BLOCK_BODY:  # block body: 1 prologue | 2 h2 | 3 mo | 4 u | 5 tail | 6 retired
             seq = [0, 1, 2, 3, 4, 5, 6]
             names = {1: "prologue", 2: "h2", 3: "mo", 4: "u", 5: "tail", 6: "retired"}
-        if op.kind == 19:  # fused SA chain: 14 prologue | 1 stage-1 K loop | 2 h2 in registers | 3 / 6 slab K loop | 4 / 7 statistics | 5 / 8 stored | 15 retired
+        if op.kind == OP_SA_CHAIN:  # fused SA chain: 14 prologue | 1 stage-1 K loop | 2 h2 in registers | 3 / 6 slab K loop | 4 / 7 statistics | 5 / 8 stored | 15 retired
             seq = [0, 14, 1, 2, 3, 4, 5] + ([6, 7, 8] if op.i[4] > 256 else []) + [15]
             names = {14: "prologue", 1: "kloop1", 2: "epi1", 3: "kloop2a", 4: "stats2a", 5: "store2a", 6: "kloop2b", 7: "stats2b", 8: "store2b", 15: "retired"}
             t[:, 6] = t[:, 15] if op.i[4] <= 256 else t[:, 6]

@@ -3,14 +3,14 @@ sys.path.insert(0, "/root/repo")
 import numpy as np, torch
 from slide_amd import configs, model_spec
 from slide_amd.diffusion import FeatureSampler
-from slide_amd.engine import SlideEpi
+from slide_amd.abi import OP_GEMM, SlideEpi
 from slide_amd.synth import synth_keypoints, synth_state_dict
 dev = torch.device("cuda:0"); B = 88
 c = configs.feature_ddpm_config()
 s = FeatureSampler(c["pointnet_config"], synth_state_dict(model_spec.denoiser_param_spec(c["pointnet_config"])), B, dev, c["standard_diffusion_config"], prec="split")
 for i in range(len(s.step_ops)):
     o = s.step_ops[i]
-    if o.kind != 1: continue
+    if o.kind != OP_GEMM: continue
     n_cob = o.i[3]
     raw = (ctypes.c_char * (ctypes.sizeof(SlideEpi) * n_cob))()
     torch.cuda.synchronize()

@@ -6,6 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from slide_amd import configs, model_spec
 from slide_amd._lib import check, lib
+from slide_amd.abi import OP_GEMM
 from slide_amd.diffusion import FeatureSampler, PositionSampler
 from slide_amd.synth import synth_keypoints, synth_state_dict
 
@@ -35,11 +36,11 @@ tot /= a.reps
 print("%3s %-7s %8s %7s %6s %6s %6s %8s %8s %8s %8s %8s" % ("#", "kind", "us", "rows", "K", "N", "npx", "GFLOP", "TFLOP/s", "rdMB", "wrMB", "GB/s"))
 for i in range(n):
     o = s.step_ops[i]
-    if o.kind == 1:
+    if o.kind == OP_GEMM:
         fl = s.gemm_flops[i]
         rd, wr = s.gemm_bytes[i]
         print("%3d %-7s %8.1f %7d %6d %6d %6d %8.2f %8.1f %8.1f %8.1f %8.0f" % (i, "GEMM", tot[i] * 1e3, o.i[0], o.i[2], o.i[3] * 32, 1 << o.i[4], fl / 1e9, fl / (tot[i] * 1e-3) / 1e12, rd / 1e6, wr / 1e6, (rd + wr) / (tot[i] * 1e-3) / 1e9))
     else:
         kn = getattr(s, "kernel_names", {}).get(i, "")
         print("%3d %-7s %8.1f   %s  i=%s" % (i, names.get(o.kind, "k%d" % o.kind), tot[i] * 1e3, kn, list(o.i)[:6]))
-print("total us %.1f  gemm us %.1f" % (tot.sum() * 1e3, sum(tot[i] for i in range(n) if s.step_ops[i].kind == 1) * 1e3))
+print("total us %.1f  gemm us %.1f" % (tot.sum() * 1e3, sum(tot[i] for i in range(n) if s.step_ops[i].kind == OP_GEMM) * 1e3))
