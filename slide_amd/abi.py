@@ -59,7 +59,7 @@ OP_POINT_CHAIN = 37
 OP_GEMM_ATTEND = 38
 OP_ROWS_PAIR_EXPAND = 39
 
-# status of an op whose kernel is not in the product library.  NOT in a header (csrc/engine.hip defines it): unchecked
+# status of an op whose kernel is not in the product library.  NOT in a header under include/ (csrc/launch.h defines it): unchecked
 ST_EXPERIMENT = -20
 
 # flag sets the headers describe in comments only (unchecked): SLIDE_OP_ROWS_GROUP i[7], SLIDE_OP_ROWS_GN i[5], SLIDE_OP_ROWS_POOL i[5],

@@ -19,12 +19,13 @@ LIB = os.path.join(HERE, "libslide_hip.so")
 LIB_EXP = os.path.join(HERE, "libslide_hip_exp.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # (source, extra flags).  point_ops and chamfer need contraction OFF (bit-exact index parity with the oracle / slide_knn_points).
-# engine: the GEMM epilogue's per-channel-block loop must unroll fully (the accumulators are indexed by it; left rolled
+# GEMM sources: the epilogue's per-channel-block loop must unroll fully (the accumulators are indexed by it; left rolled
 # they are demoted to scratch), which needs more than LLVM's default 16k-instruction cap for `#pragma unroll`.
 UNROLL = ["-mllvm", "-pragma-unroll-threshold=100000"]
 SOURCES = [("point_ops.hip", ["-ffp-contract=off"]), ("chamfer.hip", ["-ffp-contract=off"]),
            ("chamfer_pairwise.hip", ["-ffp-contract=off"]), ("chamfer_bwd.hip", ["-ffp-contract=off"]),
-           ("occupancy_grid.hip", ["-ffp-contract=off"]), ("engine.hip", UNROLL), ("gemm_gx.hip", UNROLL), ("gemm_gxs.hip", UNROLL),
+           ("occupancy_grid.hip", ["-ffp-contract=off"]), ("engine.hip", UNROLL), ("gemm_ring.hip", UNROLL), ("attn_tail.hip", UNROLL),
+           ("gemm_gx.hip", UNROLL), ("gemm_gxs.hip", UNROLL),
            ("point_chain.hip", UNROLL), ("rows_ops.hip", []), ("train_ops.hip", []),
            ("group_coord_bwd.hip", ["-ffp-contract=off"])]
 SOURCES_EXP = SOURCES + [("experiments/block_body.hip", UNROLL), ("experiments/gemm_xs.hip", UNROLL), ("experiments/gemm_chain.hip", UNROLL),
@@ -130,17 +131,20 @@ def _build_one(lib, sources, objdir, defines, lint, force, verbose):
     for src, extra in sources:
         s = os.path.join(CSRC, src)
         if not os.path.exists(s):
-            continue
+            raise FileNotFoundError("%s is listed in build.py's sources and does not exist" % s)
         o = os.path.join(objdir, os.path.basename(src).replace(".hip", ".o"))
         if force or _newer(s, o) or any(_newer(d, o) for d in deps):
             jobs.append((s, extra, o))
         objs.append(o)
-    if jobs:  # the translation units compile concurrently (hipcc is single-threaded per file; engine.hip is the long pole)
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as ex:
+    # the translation units compile concurrently (hipcc is single-threaded per file; gemm_gx.hip and gemm_ring.hip are the long
+    # poles); at most 16 at a time: os.cpu_count() reports the machine's CPUs, not what a job on a shared machine may use
+    if jobs:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), 16, os.cpu_count() or 1)) as ex:
             for f in [ex.submit(_compile, s, extra, o, defines, lint, verbose) for s, extra, o in jobs]:
                 f.result()
     if jobs or not os.path.exists(lib):
-        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs
+        # --no-undefined: a source missing from the list, or a launch.h declaration nobody defines, fails here and not at dlopen
+        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", lib] + objs
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

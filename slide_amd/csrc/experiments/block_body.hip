@@ -13,6 +13,7 @@
 // Nothing K-expanded touches memory: inputs are the per-point pair tables, outputs 16 rows per sample.  All weights stream
 // through one LDS-DMA ring of 16 KB slots whose (host-built) descriptor list runs ahead across every stage.
 #include "../gemm_common.h"
+#include "../launch.h"
 
 namespace {
 
@@ -591,15 +592,7 @@ __global__ __launch_bounds__(64 << (NPXL - 5), NPXL == 7 ? 1 : 2) void block_bod
 
 template <int NPXL, bool REST, int NB1, int NBM, int NBU>
 int launch_body(const BodyArgs &a, size_t shm, hipStream_t s) {
-  static bool attr_done[64] = {};
-  int d = 0;
-  (void)hipGetDevice(&d);
-  d = d >= 0 && d < 64 ? d : 0;
-  if (!attr_done[d]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&block_body_kernel<NPXL, REST, NB1, NBM, NBU>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done[d] = true;
-  }
+  allow_dynamic_lds<&block_body_kernel<NPXL, REST, NB1, NBM, NBU>>(160 * 1024);
   hipLaunchKernelGGL((block_body_kernel<NPXL, REST, NB1, NBM, NBU>), dim3(a.B), dim3(64 << (NPXL - 5)), shm, s, a);
   return (int)hipGetLastError();
 }

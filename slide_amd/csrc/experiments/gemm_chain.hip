@@ -3,7 +3,7 @@
 // Between the K-expanded bodies of two blocks the plan runs short chains of 16-row GEMMs: the second Mlp_plus_t_emb of an FP
 // block (first_mlp | res_connect, then second_mlp + residual: pointnet2_modules.py:842-873) and, after the last block, the
 // output head (fc_lyaer, pointnet2_with_pcld_condition.py:480-483).  Each was a launch of the split-K small kernel
-// (engine.hip): 6 .. 13 us of mostly launch / prologue / drain for a few MFLOP per sample, and -- four chains being in flight
+// (gemm_ring.hip): 6 .. 13 us of mostly launch / prologue / drain for a few MFLOP per sample, and -- four chains being in flight
 // in bench.py's arrangement -- several hundred workgroups each on the CUs the other chains' large kernels want.
 //
 // Here a workgroup owns 64 rows (four samples) and walks the chain's layers itself: a layer's GroupNorm is per sample and
@@ -16,11 +16,11 @@
 // instead of four K slices).  Layer outputs go through memory (L2) as before; a workgroup barrier after the stores orders
 // them for the next layer's staging (same CU: the vector L1 holds no line of them before that).
 #include "gemm_common.h"
+#include "launch.h"
 
 namespace {
 
 constexpr int CHAIN_MAX_LAYERS = 6;
-constexpr int SLIDE_MAX_DEVICES_C = 64;
 
 struct ChainLayer {
   const void *X, *W;
@@ -148,15 +148,7 @@ int slide_launch_gemm_chain(const SlideOp &o, hipStream_t s) {
   }
   const size_t shm = (size_t)8 * (EPI_DW + 96) * 4 + (size_t)64 * (kmax + 8) * 2;
   if (shm > 160 * 1024) return -8;
-  static bool attr_done[SLIDE_MAX_DEVICES_C] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  bool &attr_set = attr_done[dev >= 0 && dev < SLIDE_MAX_DEVICES_C ? dev : 0];
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    attr_set = true;
-  }
+  allow_dynamic_lds<&gemm_chain_kernel>(160 * 1024);
   hipLaunchKernelGGL(gemm_chain_kernel, dim3((c.rows + 63) / 64), dim3(512), shm, s, c);
   return (int)hipGetLastError();
 }

@@ -1,5 +1,6 @@
-// gemm_xs.hip -- the X-stationary GEMM of the fused denoiser plan (dispatched by engine.hip's run_gemm).
+// gemm_xs.hip -- the X-stationary GEMM of the fused denoiser plan (dispatched by gemm_ring.hip's run_gemm).
 #include "gemm_common.h"
+#include "launch.h"
 
 #include <cstdlib>
 
@@ -224,22 +225,9 @@ __global__ __launch_bounds__(256, OCC) void gemm_xs_kernel(GemmArgs a, int nstw,
   }
 }
 
-constexpr int SLIDE_MAX_DEVICES = 64;
-inline int current_device_slot() {
-  int d = 0;
-  (void)hipGetDevice(&d);
-  return d >= 0 && d < SLIDE_MAX_DEVICES ? d : 0;
-}
-
 template <int NPXL, int CBW, bool AFF, bool GAT, int OCC>
 int launch_xs(const GemmArgs &b, size_t shm, int nstw, int nsplit, int ntr8, hipStream_t s) {
-  static bool attr_done[SLIDE_MAX_DEVICES] = {};
-  bool &attr_set = attr_done[current_device_slot()];
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_xs_kernel<NPXL, CBW, AFF, GAT, OCC>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  allow_dynamic_lds<&gemm_xs_kernel<NPXL, CBW, AFF, GAT, OCC>>(160 * 1024);
   hipLaunchKernelGGL((gemm_xs_kernel<NPXL, CBW, AFF, GAT, OCC>), dim3(ntr8 * nsplit), dim3(256), shm, s, b, nstw, nsplit, ntr8);
   return (int)hipGetLastError();
 }

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "../../../include/experiments/slide_resident.h"
+#include "../launch.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -742,14 +743,7 @@ extern "C" {
 int slide_resident_run(const RArgs *args, slide_stream_t stream) {
   if (!args || args->B <= 0 || args->n_steps <= 0 || args->n_ops <= 0) return -3;
   if (args->lds_bytes > 160 * 1024 || args->cx * 16 > 256 || args->out_dim > 4) return -8;
-  static bool attr_done[64] = {};
-  int d = 0;
-  (void)hipGetDevice(&d);
-  bool &set = attr_done[d >= 0 && d < 64 ? d : 0];
-  if (!set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&resident_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    set = true;
-  }
+  allow_dynamic_lds<&resident_kernel>(160 * 1024);
   hipLaunchKernelGGL(resident_kernel, dim3(args->B), dim3(256), (size_t)args->lds_bytes, (hipStream_t)stream, *args);
   return (int)hipGetLastError();
 }

@@ -1,4 +1,4 @@
-// gemm_common.h -- shared device code of the fused-denoiser GEMM kernels (engine.hip, gemm_xs.hip): tile constants, the
+// gemm_common.h -- shared device code of the fused-denoiser GEMM kernels (gemm_ring.hip, attn_tail.hip, gemm_gx.hip, gemm_xs.hip, ...): tile constants, the
 // argument block, lane helpers and the common epilogue (bias, per-point term, ReLU, GroupNorm, t-/class-embedding add,
 // residual, stores).  Everything lives in an anonymous namespace: each translation unit gets its own copy.
 #pragma once
@@ -76,7 +76,7 @@ static inline void resolve_epi(GemmArgs &a) {
   }
 }
 
-// SLIDE_OP_PAIR_FIRST (pair_first_kernel, engine.hip): what the pair-table epilogue reads beside the GEMM arguments
+// SLIDE_OP_PAIR_FIRST (pair_first_kernel, gemm_ring.hip): what the pair-table epilogue reads beside the GEMM arguments
 struct PairArgs {
   const float *xyz;          // coordinates [B*16][3]
   const float *wa, *wb;      // coordinate coefficients of the a / b tables, [ld][4] per pair channel

@@ -22,16 +22,15 @@
 
 #include "gemm_common.h"
 #include "gemm_small.h"
+#include "launch.h"
 #include "pair_norm.h"
 
 namespace {
 
-constexpr int SLIDE_MAX_DEVICES = 64;
-
 // ------------------------------------------------------------------------------------------------ generated-X GEMM
 // Tile: 256 rows (one 16x16 sample, or two 16x8 samples) x 128 channels; four waves, wave w owns rows 64 w .. 64 w + 63 and
 // all 128 channels (acc[4][2] = 128 registers).  W: chunk-major [k / 32][n_cob * 32][32]; a ring stage is two 32-deep
-// chunk images ([128 rows][64 B], source-side XOR swizzle as in the ring kernels of engine.hip) = 16 KB; NST stages.
+// chunk images ([128 rows][64 B], source-side XOR swizzle as in the ring kernels of gemm_ring.hip) = 16 KB; NST stages.
 // Tables in LDS: [16-byte piece of the row][table row][8 halves] -- the 16 rows a ds_read_b128 lane group touches for one
 // piece are 256 consecutive bytes (conflict-free for any neighbour permutation), filled by LDS-DMA (per-lane source rows).
 // The K loop is software-pipelined by hand over its 16-deep steps: the LDS reads of step s + 1 (weight fragments, table
@@ -438,41 +437,23 @@ int launch_gx(const GemmArgs &a, hipStream_t s) {
   if (shm > (CBW == 2 && OCC3 ? 53 : 80) * 1024) return -8;
   const int ntc = (a.n_cob + CBW - 1) / CBW, ntr = (a.rows + TM - 1) / TM;
   const int grid = ((ntr + 7) / 8) * 8 * ntc;
-  static bool attr_done[SLIDE_MAX_DEVICES] = {};
-  int d = 0;
-  (void)hipGetDevice(&d);
-  bool &attr_set = attr_done[d >= 0 && d < SLIDE_MAX_DEVICES ? d : 0];
   GemmArgs b = a;
   b.shm_bytes = (int)shm;
   if constexpr (CBW == 2 && !OCC3) {
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_gx_n64w_kernel<NPXL, NST, MODE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr_set = true;
-    }
+    allow_dynamic_lds<&gemm_gx_n64w_kernel<NPXL, NST, MODE>>(160 * 1024);
     hipLaunchKernelGGL((gemm_gx_n64w_kernel<NPXL, NST, MODE>), dim3(grid), dim3(256), shm, s, b);
   } else if constexpr (CBW == 2) {
     // (red / gsh of the common epilogue live in the dead ring: 256 CBW + 128 CBW floats = 3 KB < the ring)
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_gx_n64_kernel<NPXL, NST, MODE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-      attr_set = true;
-    }
+    allow_dynamic_lds<&gemm_gx_n64_kernel<NPXL, NST, MODE>>(64 * 1024);
     hipLaunchKernelGGL((gemm_gx_n64_kernel<NPXL, NST, MODE>), dim3(grid), dim3(256), shm, s, b);
   } else {
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_gx_kernel<NPXL, NST, MODE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr_set = true;
-    }
+    allow_dynamic_lds<&gemm_gx_kernel<NPXL, NST, MODE>>(160 * 1024);
     hipLaunchKernelGGL((gemm_gx_kernel<NPXL, NST, MODE>), dim3(grid), dim3(256), shm, s, b);
   }
   return (int)hipGetLastError();
 }
 
 }  // namespace
-
-int slide_launch_gemm_gx(const SlideOp &o, hipStream_t s);
 
 static int gx_args_from_op(const SlideOp &o, GemmArgs &a) {
   a = GemmArgs();
@@ -507,15 +488,7 @@ static int launch_gx_dual(const GemmArgs &a1, const GemmArgs &a0, hipStream_t s)
   if (shm > (NPXL == 7 ? 53 : 80) * 1024) return -8;  // (three / two workgroups per CU)
   const int ntr = (a1.rows + TM - 1) / TM;
   const int g1 = ((ntr + 7) / 8) * 8 * ((a1.n_cob + 1) / 2), g0 = ((ntr + 7) / 8) * 8 * ((a0.n_cob + 1) / 2);
-  static bool attr_done[SLIDE_MAX_DEVICES] = {};
-  int d = 0;
-  (void)hipGetDevice(&d);
-  bool &attr_set = attr_done[d >= 0 && d < SLIDE_MAX_DEVICES ? d : 0];
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_gx_dual_kernel<NPXL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    attr_set = true;
-  }
+  allow_dynamic_lds<&gemm_gx_dual_kernel<NPXL>>(160 * 1024);
   GemmArgs b1 = a1, b0 = a0;
   b1.shm_bytes = b0.shm_bytes = (int)shm;
   hipLaunchKernelGGL((gemm_gx_dual_kernel<NPXL>), dim3(g1 + g0), dim3(256), shm, s, b1, b0, g1);
@@ -523,7 +496,6 @@ static int launch_gx_dual(const GemmArgs &a1, const GemmArgs &a0, hipStream_t s)
 }
 
 // SLIDE_OP_GEMM_GX_DUAL: p[0] = HOST pointer to two SlideOp (SLIDE_OP_GEMM_GX: mode 1, then mode 0) of the same block
-int slide_launch_gemm_gxs_dual(const SlideOp *pr, hipStream_t s);  // gemm_gxs.hip (split arithmetic)
 int slide_launch_gemm_gx_dual(const SlideOp &o, hipStream_t s) {
   const SlideOp *pr = (const SlideOp *)o.p[0];
   if (!pr || pr[0].kind != SLIDE_OP_GEMM_GX || pr[1].kind != SLIDE_OP_GEMM_GX) return -3;
@@ -581,7 +553,7 @@ int slide_launch_gemm_gx(const SlideOp &o, hipStream_t s) {
 }
 
 // SLIDE_OP_PAIR_NORM: the two-launch form of the pair-table pass (SLIDE_PAIR_FUSED=0) and its one-workgroup-per-sample version
-// (SLIDE_PAIR_NORM_V2=1) -- experiments build only; the default plans run SLIDE_OP_PAIR_FIRST (engine.hip)
+// (SLIDE_PAIR_NORM_V2=1) -- experiments build only; the default plans run SLIDE_OP_PAIR_FIRST (gemm_ring.hip)
 // version 2 with FLOAT tables (i[4] == 1): the pair-table pass of the split-arithmetic plans (product build)
 static int launch_pair_norm2_f32(const SlideOp &o, hipStream_t s) {
   const int B = o.i[0], ld = o.i[1], K = o.i[2];
@@ -597,15 +569,7 @@ static int launch_pair_norm2_f32(const SlideOp &o, hipStream_t s) {
                        (float *)nullptr, fin);
   else if (K == 8) {
     if (!o.p[7] || !o.p[8] || !o.p[9] || !o.p[10] || !o.p[11]) return -3;
-    static bool attr_done[64] = {};
-    int d = 0;
-    (void)hipGetDevice(&d);
-    d = d >= 0 && d < 64 ? d : 0;
-    if (!attr_done[d]) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&pair_norm2_kernel<true, float, 512>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 513 * 4);
-      attr_done[d] = true;
-    }
+    allow_dynamic_lds<&pair_norm2_kernel<true, float, 512>>(16 * 513 * 4);
     hipLaunchKernelGGL((pair_norm2_kernel<true, float, 512>), grid, blk, (size_t)16 * 513 * 4, s, ld, (const float *)o.p[0],
                        (const float *)o.p[1], (const float *)o.p[2], (const float *)o.p[3], (const SlideEpi *)o.p[4],
                        (float *)o.p[5], (float *)o.p[6], (const int *)o.p[7], (const float *)o.p[8], (const float *)o.p[9],
@@ -637,15 +601,7 @@ int slide_launch_pair_norm(const SlideOp &o, hipStream_t s) {
                          (const float *)nullptr, (float *)nullptr, fin);
     else if (K == 8) {
       if (!o.p[7] || !o.p[8] || !o.p[9] || !o.p[10] || !o.p[11]) return -3;
-      static bool attr_done[64] = {};
-      int d = 0;
-      (void)hipGetDevice(&d);
-      d = d >= 0 && d < 64 ? d : 0;
-      if (!attr_done[d]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&pair_norm2_kernel<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 1025 * 4);
-        attr_done[d] = true;
-      }
+      allow_dynamic_lds<&pair_norm2_kernel<true>>(16 * 1025 * 4);
       hipLaunchKernelGGL(pair_norm2_kernel<true>, grid, blk, (size_t)16 * 1025 * 4, s, ld, (const float *)o.p[0],
                          (const float *)o.p[1], (const float *)o.p[2], (const float *)o.p[3], (const SlideEpi *)o.p[4],
                          (_Float16 *)o.p[5], (_Float16 *)o.p[6], (const int *)o.p[7], (const float *)o.p[8],
@@ -1120,21 +1076,11 @@ int slide_launch_sa_chain_p(const SlideOp &o, hipStream_t s) {
   const int grid_p = ((g.rows + 63) / 64) * ((g.n_cob + 1) / 2);
   const size_t shm_p = (size_t)4 * 2 * 6144 + 2 * (sizeof(SlideEpi) + 96 * 4) + 32 + (size_t)4 * 2 * g.k_pad * 2 + 1024;
   const size_t shm = shm_sa > shm_p ? shm_sa : shm_p;
-  static bool attr_done[2][64] = {};
-  int d = 0;
-  (void)hipGetDevice(&d);
-  d = d >= 0 && d < 64 ? d : 0;
   if (a.n1 == 128) {
-    if (!attr_done[0][d]) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sa_chain_p_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr_done[0][d] = true;
-    }
+    allow_dynamic_lds<&sa_chain_p_kernel<4>>(160 * 1024);
     hipLaunchKernelGGL((sa_chain_p_kernel<4>), dim3(a.B * a.nsplit + grid_p), dim3(512), shm, s, a, g, a.B * a.nsplit);
   } else {
-    if (!attr_done[1][d]) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sa_chain_p_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr_done[1][d] = true;
-    }
+    allow_dynamic_lds<&sa_chain_p_kernel<8>>(160 * 1024);
     hipLaunchKernelGGL((sa_chain_p_kernel<8>), dim3(a.B * a.nsplit + grid_p), dim3(512), shm, s, a, g, a.B * a.nsplit);
   }
   return (int)hipGetLastError();
@@ -1145,21 +1091,11 @@ int slide_launch_sa_chain(const SlideOp &o, hipStream_t s) {
   size_t shm = 0;
   const int ast = sa_args_from_op(o, a, shm);
   if (ast != 0) return ast;
-  static bool attr_done[2][64] = {};
-  int d = 0;
-  (void)hipGetDevice(&d);
-  d = d >= 0 && d < 64 ? d : 0;
   if (a.n1 == 128) {
-    if (!attr_done[0][d]) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sa_chain_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr_done[0][d] = true;
-    }
+    allow_dynamic_lds<&sa_chain_kernel<4>>(160 * 1024);
     hipLaunchKernelGGL((sa_chain_kernel<4>), dim3(a.B * a.nsplit), dim3(512), shm, s, a);
   } else {
-    if (!attr_done[1][d]) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sa_chain_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr_done[1][d] = true;
-    }
+    allow_dynamic_lds<&sa_chain_kernel<8>>(160 * 1024);
     hipLaunchKernelGGL((sa_chain_kernel<8>), dim3(a.B * a.nsplit), dim3(512), shm, s, a);
   }
   return (int)hipGetLastError();

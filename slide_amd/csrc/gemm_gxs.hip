@@ -15,14 +15,13 @@
 // Reference: pointnet2_ops/pointnet2_utils.py:383-430, :497-524 (grouped inputs), pointnet2_ops/pointnet2_modules.py:119-176
 // (Mlp_plus_t_emb), pointnet2_ops/attention.py:70-96.
 #include "gemm_common.h"
+#include "launch.h"
 #include "pair_norm.h"
 
 namespace {
 
-constexpr int GXS_MAX_DEVICES = 64;
-
 __device__ __forceinline__ void gxs_split4(const float4 v, f16x4 &hi, f16x4 &lo) {
-  // x = hi + 2^-11 lo: the scaling keeps lo a normal fp16 number at any magnitude (engine.hip, gemm_kernel<SPLIT>)
+  // x = hi + 2^-11 lo: the scaling keeps lo a normal fp16 number at any magnitude (gemm_ring.hip, gemm_kernel<SPLIT>)
   hi = f16x4{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
   lo = f16x4{(_Float16)((v.x - (float)hi[0]) * 2048.f), (_Float16)((v.y - (float)hi[1]) * 2048.f),
              (_Float16)((v.z - (float)hi[2]) * 2048.f), (_Float16)((v.w - (float)hi[3]) * 2048.f)};
@@ -355,23 +354,11 @@ int launch_gxs(const GemmArgs &a, hipStream_t s) {
   if (shm > 80 * 1024) return -8;
   const int ntc = (a.n_cob + 1) / 2, ntr = (a.rows + TM - 1) / TM;
   const int grid = ((ntr + 7) / 8) * 8 * ntc;
-  static bool attr_done[GXS_MAX_DEVICES] = {};
-  int d = 0;
-  (void)hipGetDevice(&d);
-  bool &attr_set = attr_done[d >= 0 && d < GXS_MAX_DEVICES ? d : 0];
   if constexpr (CHAIN) {
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_gxs_chain_kernel<NPXL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                80 * 1024);
-      attr_set = true;
-    }
+    allow_dynamic_lds<&gemm_gxs_chain_kernel<NPXL>>(80 * 1024);
     hipLaunchKernelGGL((gemm_gxs_chain_kernel<NPXL>), dim3(grid), dim3(256), shm, s, a);
   } else {
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_gxs_kernel<NPXL, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                80 * 1024);
-      attr_set = true;
-    }
+    allow_dynamic_lds<&gemm_gxs_kernel<NPXL, MODE>>(80 * 1024);
     hipLaunchKernelGGL((gemm_gxs_kernel<NPXL, MODE>), dim3(grid), dim3(256), shm, s, a);
   }
   return (int)hipGetLastError();
@@ -382,7 +369,7 @@ int launch_gxs(const GemmArgs &a, hipStream_t s) {
 // first (accumulators -> GroupNorm statistics over the sample -> normalised in place: 64 registers), then scores S = W5 u + b5 into a
 // second accumulator set, soft-max over a point's K neighbours and the weighted sum -- S and V (2 x rows x C x 4 B, written and read
 // back by the three-launch form: 134 MB per step at the position net's SA1) never leave the registers.  Operand roles are SWAPPED
-// (A = X rows, B = W rows) as in attn_tail_kernel (engine.hip): a lane owns one channel and its registers run over the rows.
+// (A = X rows, B = W rows) as in attn_tail_kernel (attn_tail.hip): a lane owns one channel and its registers run over the rows.
 // Tile 256 rows x 64 channels, four waves x 64 rows; one LDS stage of five fp16 planes [X hi | X lo | W hi | 2^11 W hi | W lo].
 struct TailSArgs {
   const float *X1, *W1, *X2, *W2;  // scores: u [rows][x1_ld] . W5 [n_cob*32][k1];  values: mo [rows][x2_ld] . Wv [n_cob*32][k2]
@@ -566,7 +553,7 @@ __global__ __launch_bounds__(256, 2) void attn_tail_split_kernel(TailSArgs a) {
   __syncthreads();  // every wave has read the statistics: the stage is free for the score contraction
   run(a.X1, a.W1, a.x1_ld, a.k1, sacc);
   // ---- base-2 soft-max over the K neighbour rows of every point, weighted sum of the values, one row out per point.  Round 6: written
-  // like attn_tail_finish (engine.hip) -- register pairs (v_pk_fma / v_pk_add_f32), log2 e folded into the bias step and v_exp_f32 on
+  // like attn_tail_finish (attn_tail.hip) -- register pairs (v_pk_fma / v_pk_add_f32), log2 e folded into the bias step and v_exp_f32 on
   // the difference (libm's expf cost ~25 instructions per value here), v_rcp instead of an IEEE division (1 ulp), one lane-half
   // exchange for numerator and denominator together.  The scores' rounding (one fma at magnitude |s| log2 e) stays at a few 1e-6 of a
   // soft-max weight: fp32-grade (position forwards vs the fp32 mode: bench.py parity, tests/test_hip_engine.py).
@@ -820,15 +807,7 @@ int launch_gxs_dual(const GemmArgs &a1, const GemmArgs &a0, hipStream_t s) {
   if (shm > 80 * 1024) return -8;
   const int ntr = (a1.rows + TM - 1) / TM;
   const int g1 = ((ntr + 7) / 8) * 8 * ((a1.n_cob + 1) / 2), g0 = ((ntr + 7) / 8) * 8 * ((a0.n_cob + 1) / 2);
-  static bool attr_done[GXS_MAX_DEVICES] = {};
-  int d = 0;
-  (void)hipGetDevice(&d);
-  bool &attr_set = attr_done[d >= 0 && d < GXS_MAX_DEVICES ? d : 0];
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_gxs_dual_kernel<NPXL, CHAIN>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              80 * 1024);
-    attr_set = true;
-  }
+  allow_dynamic_lds<&gemm_gxs_dual_kernel<NPXL, CHAIN>>(80 * 1024);
   hipLaunchKernelGGL((gemm_gxs_dual_kernel<NPXL, CHAIN>), dim3(g1 + g0), dim3(256), shm, s, a1, a0, g1);
   return (int)hipGetLastError();
 }
@@ -878,7 +857,7 @@ int slide_launch_attn_tail_split(const SlideOp &o, hipStream_t s) {
 //   pair : slot 0 = 1, [1] y, [2] xyz, [3] wa, [4] wb, [5] epi, [6] ta, [7] tb, [8] nbr, [9] d2, [10] w, [11] vv_in, [12] vv_out, [13] SlideGnFin*,
 //          [14] ld, [15] K
 #ifndef SLIDE_EXPERIMENTS
-int slide_launch_pp_stage(const SlideOp &, hipStream_t) { return -20; }  // experiments build only
+int slide_launch_pp_stage(const SlideOp &, hipStream_t) { return SLIDE_ST_EXPERIMENT; }
 #else
 int slide_launch_pp_stage(const SlideOp &o, hipStream_t s) {
   const int64_t *h = (const int64_t *)o.p[0];

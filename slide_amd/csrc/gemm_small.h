@@ -1,4 +1,4 @@
-// gemm_small.h -- the split-K small-launch GEMM body (16 rows per sample), shared by engine.hip (gemm_small_kernel,
+// gemm_small.h -- the split-K small-launch GEMM body (16 rows per sample), shared by gemm_ring.hip (gemm_small_kernel,
 // pair_first_kernel) and gemm_gx.hip (sa_chain_p_kernel: the per-point query GEMM of an SA block riding on the launch of its
 // fused Mlp chain).  Anonymous namespace: every translation unit gets its own copy.
 #pragma once

@@ -1,0 +1,68 @@
+// launch.h -- what crosses translation units inside the library (internal: not part of the C ABI under include/): the launch
+// entry points that one .hip defines and another calls, the experiments-only status, and the per-device first-use helper of the
+// dynamic-LDS limit.  Every .hip that defines or calls one of these functions includes this header, so a drifted signature fails
+// to compile in the defining file (the library is also linked with --no-undefined: a forgotten source fails the link).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/slide_engine.h"
+
+struct GemmArgs;  // gemm_common.h
+
+// Status of an op whose kernel only exists in the EXPERIMENTS build (slide_amd/build.py: libslide_hip_exp.so, -DSLIDE_EXPERIMENTS):
+// the opt-in variants that lost their A/Bs (X-stationary tiles, per-point layer chains, head + update launch, wide / eight-wave
+// attention tails, 128- / 32-channel and 64-deep ring tiles, the round-2 plan's gathered first layers, the register-staged fp16
+// GEMM).  The product library carries only what a default plan dispatches.
+#define SLIDE_ST_EXPERIMENT (-20)
+
+// gemm_ring.hip: SLIDE_OP_GEMM, SLIDE_OP_PAIR_FIRST, SLIDE_OP_GEMM_ATTEND
+int slide_launch_gemm(const SlideOp &o, hipStream_t s);
+int slide_launch_pair_first(const SlideOp &o, hipStream_t s);
+int slide_launch_gemm_attend(const SlideOp &o, hipStream_t s);
+// attn_tail.hip: the fused attention tails (fp16)
+int slide_launch_attn_tail(const SlideOp &o, hipStream_t s);
+// rows_ops.hip: the row-major ops of the module path
+int slide_launch_rows_op(const SlideOp &o, hipStream_t s);
+// point_chain.hip
+int slide_launch_point_chain(const SlideOp &o, hipStream_t s);
+// gemm_gx.hip: generated-X GEMM and the per-point table normalisation of the pair decomposition
+int slide_launch_gemm_gx(const SlideOp &o, hipStream_t s);
+int slide_launch_gemm_gx_dual(const SlideOp &o, hipStream_t s);
+int slide_launch_pair_norm(const SlideOp &o, hipStream_t s);
+int slide_launch_sa_chain(const SlideOp &o, hipStream_t s);
+int slide_launch_sa_chain_p(const SlideOp &o, hipStream_t s);
+// gemm_gxs.hip: the same in split arithmetic (float tables), the split attention tail, the per-point MFMA stages
+int slide_launch_gemm_gxs(const SlideOp &o, hipStream_t s);
+int slide_launch_gemm_gxs_dual(const SlideOp *pr, hipStream_t s);
+int slide_launch_attn_tail_split(const SlideOp &o, hipStream_t s);
+int slide_launch_pp_stage(const SlideOp &o, hipStream_t s);
+// experiments/block_body.hip (called in the experiments build only)
+int slide_launch_block_body(const SlideOp &o, hipStream_t s);
+#ifdef SLIDE_EXPERIMENTS
+// experiments/gemm_xs.hip: X-stationary kernel (-8: the X tile does not fit the LDS, -4: no such instantiation)
+int slide_launch_gemm_xs(const GemmArgs &a, int npxl, int cbw, bool aff, bool gat, int want_occ, hipStream_t s);
+// experiments/gemm_chain.hip
+int slide_launch_gemm_chain(const SlideOp &o, hipStream_t s);
+#endif
+
+// hipFuncSetAttribute is per device: the "already raised the dynamic-LDS limit" flags are kept per device so that one
+// process may drive plans on several GPUs (first use of a kernel on each device must still happen outside stream capture
+// and from one thread, as for any lazily initialised runtime state)
+constexpr int SLIDE_MAX_DEVICES = 64;
+inline int current_device_slot() {
+  int d = 0;
+  (void)hipGetDevice(&d);
+  return d >= 0 && d < SLIDE_MAX_DEVICES ? d : 0;
+}
+
+// once per (kernel, device): raise the kernel's dynamic-LDS limit.  Kernel is the address of a __global__ function or of one
+// instantiation of a kernel template (allow_dynamic_lds<&k<3, true>>(bytes)): each gets its own flags.
+template <auto Kernel>
+inline void allow_dynamic_lds(int bytes) {
+  static bool done[SLIDE_MAX_DEVICES] = {};
+  bool &set = done[current_device_slot()];
+  if (!set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    set = true;
+  }
+}

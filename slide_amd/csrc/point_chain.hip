@@ -24,6 +24,7 @@
 // stores of 1632 elements per workgroup cost more than the 71-workgroup launch they replace (round 4's head_update_kernel: -1.4 %).
 #include "gemm_common.h"
 #include "ddpm_update.h"
+#include "launch.h"
 
 namespace {
 

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "../../include/slide_engine.h"
+#include "launch.h"
 
 namespace {
 

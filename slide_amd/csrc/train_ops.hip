@@ -1,6 +1,6 @@
 // train_ops.hip -- gfx950 BACKWARD kernels of the row-major layers (the training step).
 //
-// The forward kernels are the module path's (rows_ops.hip: grouping, GroupNorm, relu([q | k]), softmax-weighted sum; engine.hip:
+// The forward kernels are the module path's (rows_ops.hip: grouping, GroupNorm, relu([q | k]), softmax-weighted sum; gemm_ring.hip:
 // the MFMA GEMM); this file holds what torch.autograd needs from each of them, on the same [rows][ld] fp32 matrices (ld = channels
 // rounded up to 32, pad columns zero).  Reference semantics being differentiated:
 //   MyGroupNorm + ReLU            pointnet2_ops_lib/pointnet2_ops/pointnet2_modules.py:24-69

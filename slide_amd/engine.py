@@ -156,14 +156,14 @@ class DenoiserEngine:
     def _tail_fm(self, mpfx, apfx, npx_log2, n_mo):
         """round 6: are the K-expanded inputs u / mo of this attention block's fused tail stored FRAGMENT-major (SLIDE_F_OUT_FM,
         include/slide_engine.h: a chunk-major slab whose 32-row groups are ordered as the MFMA fragments the register-X tail
-        kernel loads -- 1 KB of consecutive memory per wave load)?  Exactly when run_attn_tail (csrc/engine.hip) picks
+        kernel loads -- 1 KB of consecutive memory per wave load)?  Exactly when run_attn_tail (csrc/attn_tail.hip) picks
         attn_tail_rx_kernel for it: fp16 pair-decomposition plan (its generated-X kernels and the SA chain are the producers that
         can store the layout), fused tail, values' chunk count a multiple of 4, none
         of the opt-in tail forms.  SLIDE_FM=0: chunk-major u / mo (A/B)."""
         env = os.environ.get
         cout = self.sd[apfx + ".weight_conv.5.weight"].shape[0]
         # mo's producer must be one that stores the layout: the generated-X GEMM of a two-layer Mlp, or the SA chain -- a rest_mlp
-        # outside the chain is a ring GEMM over a stored h2 (engine.hip: its epilogue instantiations do not carry the layout)
+        # outside the chain is a ring GEMM over a stored h2 (gemm_ring.hip: its epilogue instantiations do not carry the layout)
         if (mpfx + ".rest_mlp.0.weight") in self.sd and not self._sa_chain_shapes(mpfx, npx_log2):
             return False
         return bool(self.use_cm and self.use_gx and self.prec == 1 and self.use_glds and env("SLIDE_FM", "1") != "0"
@@ -672,7 +672,7 @@ class DenoiserEngine:
             off += Op
         ldy = off
         # SLIDE_PAIR_FUSED (default on): the per-point GEMM and the pair-table pass as ONE launch (SLIDE_OP_PAIR_FIRST,
-        # csrc/engine.hip pair_first_kernel) -- y never goes through memory; bit-identical to the two-launch form
+        # csrc/gemm_ring.hip pair_first_kernel) -- y never goes through memory; bit-identical to the two-launch form
         fused = fin is None and self.prec == 1 and self.use_glds and os.environ.get("SLIDE_PAIR_FUSED", "1") != "0"
         Y = None if fused else self.A.zeros(B * 16, ldy)  # fp32
         wa, wb, vv_in = np.zeros((ldy, 4), np.float32), np.zeros((ldy, 4), np.float32), np.zeros((2, ldy), np.float32)

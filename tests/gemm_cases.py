@@ -1,7 +1,7 @@
 """The SLIDE_OP_GEMM case matrix, its float64 reference, its error bounds and its mutants -- shared by
 tests/test_hip_gemm_arith.py (every case on the GPU against the reference, and, on the CPU, every bound against the mutants).
 
-A case is one GEMM launch of `run_gemm` (csrc/engine.hip): y = X' . W^T + bias (+ pre_add) -> epilogue (include/slide_engine.h,
+A case is one GEMM launch of `run_gemm` (csrc/gemm_ring.hip): y = X' . W^T + bias (+ pre_add) -> epilogue (include/slide_engine.h,
 SlideEpi).  X' is X, or with an input affine X * scale + shift of the row's sample.  The reference takes the operands as the
 kernel reads them:
   fp32, split: the fp32 values of X, W, scale, shift, residual, pre_add, tables (split rebuilds fp32-grade products from them);

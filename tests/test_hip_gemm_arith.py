@@ -2,7 +2,7 @@
 bounds derived from the arithmetic (tests/gemm_cases.py: the case matrix, the reference, the derivation of the bounds and the
 mutants they must see).
 
-Every product-build branch of run_gemm (csrc/engine.hip) has a case:
+Every product-build branch of run_gemm (csrc/gemm_ring.hip) has a case:
   branch                                               | cases
   launch_gemm<F32, 4 / 7 / 8, 2>                       | f32_n4_*, f32_n7_*, f32_n8_*
   launch_gemm<SPLIT, 7 / 8, 2>                         | split_n7_norm, split_n7_stats, split_n8_raw, split_n8_norm_aff

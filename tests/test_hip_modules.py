@@ -755,7 +755,7 @@ def test_pair_decomposition_of_the_module_path(gpu_device, monkeypatch, layout):
 
 def test_deferred_normalisation_matches_the_materialised_path(gpu_device, monkeypatch):
     """fp16 module path: a GroupNorm whose consumer is a GEMM is DEFERRED -- the producer's raw output stays in memory and the
-    consumer's loader applies relu(x * scale + shift) + add from per-sample fp16 vectors in LDS (csrc/engine.hip, AFF
+    consumer's loader applies relu(x * scale + shift) + add from per-sample fp16 vectors in LDS (csrc/gemm_ring.hip, AFF
     loaders) -- where SLIDE_MODULE_DEFER=0 normalises in fp32 arithmetic first and stores the fp16 result.  The two differ by
     the fp16 rounding of scale / shift / add (2^-11 relative each) and of the affine's result: bounded here on activations
     with a large mean (|shift| = mean * rstd ~ 6) and large embedding rows (|add| up to 50), where that rounding is at its
