@@ -20,7 +20,7 @@ import torch
 from ._lib import check, lib
 from .abi import (OP_ADVANCE_T, OP_ATTN_TAIL, OP_GEMM, OP_HEAD_UPDATE, OP_POINT_CHAIN, OP_PREP_POINTS, OP_SYNC, OP_UPDATE_FEAT,
                   OP_UPDATE_POS, SlideHeadArgs, SlideOp, make_op)
-from .engine import DenoiserEngine
+from .engine import DenoiserEngine, accounting
 
 F32 = np.float32
 
@@ -110,6 +110,23 @@ def _masked_stream_return(key, handle):
     _MASKED_FREE.setdefault(key, []).append(handle)  # (never destroyed: see above)
 
 
+def _copy_update(h, u):
+    """the fields of an update op (SLIDE_OP_UPDATE_POS / SLIDE_OP_UPDATE_FEAT) in a SlideHeadArgs-shaped block: what the fused forms of
+    the update (SLIDE_OP_HEAD_UPDATE, the point chain's update) read in its place"""
+    h.x, h.noise, h.t_dev = u.p[0], u.p[2], u.p[3]
+    if u.kind == OP_UPDATE_POS:
+        h.kind, h.C, h.kdim = 0, 3, 0
+        h.seed_lo, h.seed_hi = u.i[2] & 0xFFFFFFFF, u.i[3] & 0xFFFFFFFF
+        h.t0, h.t1, h.t2 = u.p[4], u.p[5], u.p[6]
+    else:
+        h.kind, h.C, h.kdim = 1, u.i[1], u.i[2]
+        h.seed_lo, h.seed_hi = u.i[3] & 0xFFFFFFFF, u.i[4] & 0xFFFFFFFF
+        h.clamp = u.f[0]
+        h.keypoint, h.t0, h.t1, h.t2, h.t3, h.t4 = u.p[4], u.p[5], u.p[6], u.p[7], u.p[8], u.p[9]
+        h.complete_x0, h.kmask = u.p[10], u.p[11]
+        h.feat0, h.ldf, h.half_out, h.copies, h.n_copies = u.p[12], u.i[6], u.i[7], u.p[13], u.i[8]
+
+
 class _GraphedSampler:
     def __init__(self, hp, state_dict, batch, device, prec, use_graph, T, cu_share=0.0, stream=None):
         self.engine = DenoiserEngine(hp, state_dict, batch, device, prec=prec, per_sample_t=False, t_table=T)
@@ -189,18 +206,7 @@ class _GraphedSampler:
             h.X, h.W0, h.W1, h.v0, h.b1 = (head[k_].data_ptr() for k_ in ("X", "W0", "W1", "v0", "b1"))
             h.eps_out = None
             h.rows, h.x_ld, h.k0, h.n1c, h.eps_ld = self.B * 16, head["X"].shape[1], head["k0"], head["n1c"], e.eps_pad.shape[1]
-            h.x, h.noise, h.t_dev = u.p[0], u.p[2], u.p[3]
-            if u.kind == OP_UPDATE_POS:
-                h.kind, h.C, h.kdim = 0, 3, 0
-                h.seed_lo, h.seed_hi = u.i[2] & 0xFFFFFFFF, u.i[3] & 0xFFFFFFFF
-                h.t0, h.t1, h.t2 = u.p[4], u.p[5], u.p[6]
-            else:
-                h.kind, h.C, h.kdim = 1, u.i[1], u.i[2]
-                h.seed_lo, h.seed_hi = u.i[3] & 0xFFFFFFFF, u.i[4] & 0xFFFFFFFF
-                h.clamp = u.f[0]
-                h.keypoint, h.t0, h.t1, h.t2, h.t3, h.t4 = u.p[4], u.p[5], u.p[6], u.p[7], u.p[8], u.p[9]
-                h.complete_x0, h.kmask = u.p[10], u.p[11]
-                h.feat0, h.ldf, h.half_out, h.copies, h.n_copies = u.p[12], u.i[6], u.i[7], u.p[13], u.i[8]
+            _copy_update(h, u)
             self._head_args = h  # (kept alive: the op carries its address)
             update_op = make_op(OP_HEAD_UPDATE, p=(ctypes.addressof(h),))
             drop = drop | set(head["idx"])
@@ -215,14 +221,7 @@ class _GraphedSampler:
             # Box-Muller draws (precise logf / cosf) and the update's scattered 4-byte stores of 1632 elements on 256 threads
             # outweigh the 71-workgroup update launch they replace, as they did in round 4's head_update_kernel
             if update_op.kind == OP_UPDATE_FEAT and os.environ.get("SLIDE_POINT_CHAIN_UPDATE", "0") != "0":
-                u, h = update_op, c.upd
-                h.kind, h.C, h.kdim = 1, u.i[1], u.i[2]
-                h.seed_lo, h.seed_hi = u.i[3] & 0xFFFFFFFF, u.i[4] & 0xFFFFFFFF
-                h.clamp = u.f[0]
-                h.x, h.noise, h.t_dev = u.p[0], u.p[2], u.p[3]
-                h.keypoint, h.t0, h.t1, h.t2, h.t3, h.t4 = u.p[4], u.p[5], u.p[6], u.p[7], u.p[8], u.p[9]
-                h.complete_x0, h.kmask = u.p[10], u.p[11]
-                h.feat0, h.ldf, h.half_out, h.copies, h.n_copies = u.p[12], u.i[6], u.i[7], u.p[13], u.i[8]
+                _copy_update(c.upd, update_op)
                 c.fuse_update = 1
                 update_op = None
             self._chain_args = c  # (kept alive: the op carries its address)
@@ -237,9 +236,7 @@ class _GraphedSampler:
         kept = [i for i in range(len(e.ops)) if i not in drop]
         ops = [e.ops[i] if i != chain_at else make_op(OP_POINT_CHAIN, p=(ctypes.addressof(self._chain_args),)) for i in kept]
         # per-launch accounting of the engine, re-keyed by position in the step plan
-        self.gemm_flops = {j: e.gemm_flops[i] for j, i in enumerate(kept) if i in e.gemm_flops}
-        self.gemm_bytes = {j: e.gemm_bytes[i] for j, i in enumerate(kept) if i in e.gemm_bytes}
-        self.kernel_names = {j: e.kernel_names[i] for j, i in enumerate(kept) if i in getattr(e, "kernel_names", {})}
+        self.gemm_flops, self.gemm_bytes, self.kernel_names = accounting([e.plan[i] for i in kept])
         if chain_at is not None and chain_at in kept:  # the chain launch stands for its four layers
             j = kept.index(chain_at)
             self.gemm_flops[j] = sum(e.gemm_flops.get(i, 0) for i in pch["idx"])

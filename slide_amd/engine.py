@@ -60,6 +60,59 @@ class _Arena:
         return t
 
 
+def _dp(t):
+    """data_ptr() of a tensor as make_op takes it (None stays None: a NULL pointer)"""
+    return None if t is None else t.data_ptr()
+
+
+class Launch:
+    """one launch of a plan with what the host knows about it: the op, its accounting -- FLOPs, algorithmic HBM bytes (read, written),
+    rocprofv3 kernel name (bench.py's roofline attribution); None where nothing was recorded -- and its roles.  A role says what the
+    rest of the host code wants this launch for: "prep" (point preparation), "eps_copy" (compaction of the prediction), "xyz_copy"
+    (reads nothing but the coordinates), "head0" / "head1" (output head layers), "pc0" .. "pc3" (layers of the point chain).  The merge
+    passes carry all of it along (`merged`); positions in the plan are derived once, at the end (`plan_tables`).
+    body: the BodyArgs of a SLIDE_OP_BLOCK_BODY launch; w16: the float weights of a per-point layer _merge_pp may fold."""
+    __slots__ = ("op", "flops", "nbytes", "name", "roles", "body", "w16")
+
+    def __init__(self, op, flops=None, nbytes=None, name=None, roles=(), body=None, w16=None):
+        self.op, self.flops, self.nbytes, self.name, self.roles, self.body, self.w16 = op, flops, nbytes, name, set(roles), body, w16
+
+
+def merged(op, name, parts):
+    """the launch that stands for `parts`: their summed FLOPs and bytes, the union of their roles"""
+    return Launch(op, sum(p.flops or 0 for p in parts), tuple(sum((p.nbytes or (0, 0))[z] for p in parts) for z in (0, 1)), name,
+                  set().union(*(p.roles for p in parts)))
+
+
+def rewrite(plan, match):
+    """one peephole pass.  match(plan, i) -> None (the launch stays) or (n, out): the n launches from i are replaced by `out`, whose
+    items are launches of the plan (kept as they are) or the arguments of `merged`"""
+    new, i = [], 0
+    while i < len(plan):
+        m = match(plan, i)
+        n, out = (1, [plan[i]]) if m is None else m
+        new += [r if isinstance(r, Launch) else merged(*r) for r in out]
+        i += n
+    return new
+
+
+def accounting(plan):
+    """(gemm_flops, gemm_bytes, kernel_names) of a launch list, keyed by position"""
+    return tuple({k: getattr(e, f) for k, e in enumerate(plan) if getattr(e, f) is not None} for f in ("flops", "nbytes", "name"))
+
+
+def plan_tables(plan):
+    """everything that is read by position in a finished launch list.  head / point_chain: the positions of the two / four launches
+    with those roles, None unless they are distinct launches (the point chain's: consecutive ones) -- a merge pass took them"""
+    at = lambda *roles: [k for r in roles for k, e in enumerate(plan) if r in e.roles]
+    flops, nbytes, names = accounting(plan)
+    head, pc = at("head0", "head1"), at("pc0", "pc1", "pc2", "pc3")
+    return dict(ops=[e.op for e in plan], gemm_flops=flops, gemm_bytes=nbytes, kernel_names=names, xyz_copy_idx=sorted(at("xyz_copy")),
+                eps_copy_idx=(at("eps_copy") or [None])[0], prep_idx=(at("prep") or [None])[0],
+                head=head if len(head) == 2 and head[0] != head[1] else None,
+                point_chain=pc if len(pc) == 4 and pc == list(range(pc[0], pc[0] + 4)) else None)
+
+
 class DenoiserEngine:
     NP = 16  # latent points per sample
     # chunk-major storage (see _buf): off unless __init__ enables it (bare plan builders in tests / tools stay row-major)
@@ -76,15 +129,13 @@ class DenoiserEngine:
         path is evaluated ONCE for all t in [0, t_table) into a table that the GEMM epilogues index with t_dev[0]."""
         lib()  # fail loudly if the HIP library is missing
         # a plan may be BUILT on the CPU device (structure / FLOP checks in the CPU tests); it can only RUN on a GPU
-        self.hp, self.B, self.device = hp, int(batch), device
-        self.prec = PREC[prec]
+        self._plan_state(batch, device, prec)
+        self.hp = hp
         self.per_sample_t = per_sample_t
         self.t_table = int(t_table)
         assert per_sample_t or t_table > 0
-        self.adt = torch.float16 if self.prec == 1 else torch.float32  # activation storage type
-        import os as _os
-        self.use_glds = _os.environ.get("SLIDE_GLDS", "1") != "0"  # LDS-DMA GEMM variant for fp16 GEMMs
-        self.glds_nst = int(_os.environ.get("SLIDE_GLDS_WIDE", "0"))  # 1: 64-deep K chunks (full cache lines)
+        self.use_glds = os.environ.get("SLIDE_GLDS", "1") != "0"  # LDS-DMA GEMM variant for fp16 GEMMs
+        self.glds_nst = int(os.environ.get("SLIDE_GLDS_WIDE", "0"))  # 1: 64-deep K chunks (full cache lines)
         self.sd = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)).astype(np.float32)
                    for k, v in state_dict.items()}
         arch = hp["architecture"]
@@ -97,16 +148,15 @@ class DenoiserEngine:
         self.cx = 3 + hp["in_fea_dim"]
         self.out_dim = hp["out_dim"]
         self.t_dim = hp["t_dim"]
-        self.A = _Arena(device)
         # chunk-major activations / weights for the 128- and 256-row ring kernels (SLIDE_CM=0: row-major everywhere, A/B)
-        self.use_cm = (self.prec == 1 and self.use_glds and self.glds_nst != 1 and _os.environ.get("SLIDE_CM", "1") != "0"
-                       and not _os.environ.get("SLIDE_XS", ""))
+        self.use_cm = (self.prec == 1 and self.use_glds and self.glds_nst != 1 and os.environ.get("SLIDE_CM", "1") != "0"
+                       and not os.environ.get("SLIDE_XS", ""))
         # pair decomposition of the blocks' first layers + generated-X GEMMs (csrc/gemm_gx.hip; SLIDE_GX=0: the round-2 plan)
-        self.use_gx = self.use_cm and _os.environ.get("SLIDE_GX", "1") != "0"
+        self.use_gx = self.use_cm and os.environ.get("SLIDE_GX", "1") != "0"
         # round 5: the pair decomposition in the SPLIT arithmetic (csrc/gemm_gxs.hip): float pair tables, generated-X split GEMMs,
         # PAIR residuals on float rows, the split attention tail -- the K-expanded first-layer outputs, scores and values of a block
         # never reach memory (SLIDE_GXS=0: the fp32-structured plan of round 4)
-        self.use_gxs = self.prec == 2 and _os.environ.get("SLIDE_GXS", "1") != "0"
+        self.use_gxs = self.prec == 2 and os.environ.get("SLIDE_GXS", "1") != "0"
         if self.use_gxs:
             # its kernels run the split products on ONE accumulator set with the weight's high term scaled by 2^11 in fp16 (DESIGN.md
             # section 5): exact while |w| < 32.  A checkpoint with a larger convolution weight takes the fp32-structured split plan.
@@ -119,14 +169,21 @@ class DenoiserEngine:
         self._cm = set()
         self._fm = set()  # chunk-major buffers whose 32-row groups are fragment-major (_tail_fm)
         self._cm_copy = {}  # per-point table (data_ptr) -> its chunk-major copy, written by the table's producer as well
-        self.ops = []
-        self._w16 = {}
-        self._w16_next = None
-        self._lane = 0
-        self.two_lanes = _os.environ.get("SLIDE_TWO_LANES", "0") != "0"  # measured: no gain at batch 256
+        self.two_lanes = os.environ.get("SLIDE_TWO_LANES", "0") != "0"  # measured: no gain at batch 256
         self._tvec = []   # (name, width) of every Mlp .fc           -> offsets into the t vector
         self._cvec = []   # (name, width) of every Mlp .fc_condition -> offsets into the condition vector
         self._build()
+
+    def _plan_state(self, batch, device, prec):
+        """the state the emitters below read and write while a plan is built; bare builders (one-op tests and tools) call this in
+        place of __init__.  The knobs are at their defaults here: __init__ / _build read the environment"""
+        self.B, self.device, self.prec = int(batch), device, PREC[prec]
+        self.adt = torch.float16 if self.prec == 1 else torch.float32  # activation storage type
+        self.A = _Arena(device)
+        self.plan, self.flops = [], 0  # the launches (Launch), in order; total FLOPs
+        self.per_sample_t = True
+        self._lane, self.two_lanes = 0, False
+        self.use_glds, self.glds_nst, self.persistent = True, 0, 0
 
     # ------------------------------------------------------------------ small helpers
     def _w(self, name):
@@ -181,17 +238,24 @@ class DenoiserEngine:
             return t.data_ptr() + t.element_size() * ((col // 32) * t.shape[0] * 32 + col % 32)
         return t.data_ptr() + t.element_size() * col
 
-    def _emit(self, op):
+    @property
+    def ops(self):
+        """the plan's ops, in order.  Assigning a list of bare ops starts a plan of them (no accounting, no roles)"""
+        return [e.op for e in self.plan]
+
+    @ops.setter
+    def ops(self, ops):
+        self.plan = [Launch(o) for o in ops]
+
+    def _emit(self, op, flops=None, nbytes=None, name=None, role=None, **kw):
+        """appends a launch to the plan with its accounting and role (Launch); returns the entry"""
         op.i[10] = self._lane if self.two_lanes else 0
-        self.ops.append(op)
-        w16 = getattr(self, "_w16_next", None)
-        if w16 is not None:
-            self._w16[id(op)] = (op, w16)
-            self._w16_next = None
+        self.plan.append(Launch(op, flops, nbytes, name, () if role is None else (role,), **kw))
+        return self.plan[-1]
 
     def _sync(self, frm, to):
         if self.two_lanes:
-            self.ops.append(make_op(OP_SYNC, i=(frm, to)))
+            self.plan.append(Launch(make_op(OP_SYNC, i=(frm, to))))
 
     def _sched(self):
         """tile counters of one persistent GEMM launch (9 ints, zero; the kernel re-arms them itself)"""
@@ -207,7 +271,7 @@ class DenoiserEngine:
         self._cvec.append((prefix, width))
         return off
 
-    def _gemm(self, X, npx_log2, segs, in_cols=None, in_affine=None, k_logical=None, gather=None, gn_fin=None,
+    def _gemm(self, X, npx_log2, segs, in_cols=None, in_affine=None, gather=None, gn_fin=None,
               pre_gather=None, gx=None, pair_tabs=None, pair_fused=None, defer=None, chain=None):
         """X: input buffer [rows][ld].  segs: list of dicts describing consecutive output segments:
              w (O,I) bias (O) | out (tensor) out_coff | mode flags | gn=(gamma,beta) for NORM | layout (gn_layout) |
@@ -357,21 +421,19 @@ class DenoiserEngine:
             return dict(W=Wd, epi=ed, epi_ptr=edp, n_cob=n_cob, k_pad=ld, flops=2 * rows * sum(int(s_["w"].size) for s_ in segs),
                         wr=sum(rows * v[2] * v[1]["out"].element_size() for v in vec_list), wbytes=W.size * 4)
         if gx is not None:
-            return self._emit_gx(gx, npx_log2, rows, ld, n_cob, Wd, edp, segs, W, vec_list, in_affine, pair_tabs, chain=chain, keep=ed)
+            return self._emit_gx(gx, npx_log2, rows, ld, n_cob, Wd, edp, segs, W, vec_list, in_affine, pair_tabs, chain=chain)
         if pair_fused is not None:  # SLIDE_OP_PAIR_FIRST: per-point GEMM + pair-table pass in one launch (_pair_first)
             pf = pair_fused
             assert npx_log2 == 4 and self.prec == 1 and in_affine is None and gather is None and gn_fin is None and not w_cm
             assert X.dtype == self.adt and not self._is_cm(X)
-            self.gemm_flops[len(self.ops)] = 2 * rows * sum(int(s_["w"].size) for s_ in segs)
-            self.gemm_bytes[len(self.ops)] = (rows * ld * 2 + W.size * 2, 2 * rows * pf["ld"] * 2 + rows * 32 * pf["cob0"] * 2)
-            self.flops += 2 * rows * sum(int(s_["w"].size) for s_ in segs)
-            self.kernel_names[len(self.ops)] = "pair_first_kernel<%s>" % ("true" if pf["K"] == 8 else "false")
-            ptr = lambda t: None if t is None else t.data_ptr()
-            self._emit(make_op(OP_PAIR_FIRST, i=(rows, x_ld, ld, n_cob, pf["cob0"], pf["ld"], pf["K"]),
-                               p=(X.data_ptr(), Wd.data_ptr(), edp, self.xyz.data_ptr(), pf["wa"].data_ptr(),
-                                  pf["wb"].data_ptr(), pf["ta"].data_ptr(), pf["tb"].data_ptr(), ptr(pf.get("nbr")), ptr(pf.get("d2")),
-                                  ptr(pf.get("w")), ptr(pf.get("vv_in")), ptr(pf.get("vv")))))
-            return
+            fl = 2 * rows * sum(int(s_["w"].size) for s_ in segs)
+            self.flops += fl
+            return self._emit(make_op(OP_PAIR_FIRST, i=(rows, x_ld, ld, n_cob, pf["cob0"], pf["ld"], pf["K"]),
+                                      p=(X.data_ptr(), Wd.data_ptr(), edp, self.xyz.data_ptr(), pf["wa"].data_ptr(),
+                                         pf["wb"].data_ptr(), pf["ta"].data_ptr(), pf["tb"].data_ptr(), _dp(pf.get("nbr")),
+                                         _dp(pf.get("d2")), _dp(pf.get("w")), _dp(pf.get("vv_in")), _dp(pf.get("vv")))),
+                              flops=fl, nbytes=(rows * ld * 2 + W.size * 2, 2 * rows * pf["ld"] * 2 + rows * 32 * pf["cob0"] * 2),
+                              name="pair_first_kernel<%s>" % ("true" if pf["K"] == 8 else "false"))
         assert X.dtype == self.adt
         # wide (128-channel) tiles only when the grid still covers the 256 CUs at least twice
         ntr = (rows + 255) // 256
@@ -379,13 +441,12 @@ class DenoiserEngine:
         # narrow launches: 32-channel tiles double the workgroups and halve each wave's epilogue while they still fit one round
         if (self.prec == 1 and self.use_glds and sc is None and npx_log2 >= 7 and ntr * n_cob <= int(os.environ.get('SLIDE_CBW1_TILES', '0'))):
             cbw = 1
-        self.gemm_flops[len(self.ops)] = 2 * rows * sum(int(s["w"].size) for s in segs)
+        fl = 2 * rows * sum(int(s["w"].size) for s in segs)
         esz = X.element_size()
         rd = rows * ld * esz + W.size * esz + sum(rows * v[2] * esz for v in vec_list if v[1].get("residual") is not None)
         rd += sum((rows >> max(v[1]["pre_add"][1], 0) if v[1]["pre_add"][1] >= 0 else rows >> npx_log2 << 4) * v[2] * esz
                   for v in vec_list if v[1].get("pre_add") is not None)  # per-point tables (unique rows)
         wr = sum(rows * v[2] * v[1]["out"].element_size() for v in vec_list)
-        self.gemm_bytes[len(self.ops)] = (rd, wr)  # algorithmic HBM bytes (read, written) of this launch
         glds = int(self.use_glds and self.prec == 1 and (sc is None or npx_log2 >= 7))
         # X-stationary kernel (csrc/gemm_xs.hip: a workgroup keeps its input resident in LDS -- for the GATHERED first layers
         # of the SA / FP blocks only the 16-row point table + the coordinate chunk, 24 KB instead of a 144 KB X tile -- and
@@ -415,33 +476,27 @@ class DenoiserEngine:
         if wfrag is not None and os.environ.get("SLIDE_XS_OCC"):
             knob = 10 + int(os.environ["SLIDE_XS_OCC"])  # cap the workgroups per CU of the X-stationary kernel (A/B timing)
         has_pair = any(v[1].get("res_pair") is not None for v in vec_list)  # -> the kernels compiled with the PAIR residual
-        if self.use_gxs and npx_log2 == 4 and gather is None and gn_fin is None and pre_gather is None and wfrag is None and \
-                not any(v[1].get("pre_add") is not None for v in vec_list):
-            self._w16_next = W  # (a per-point layer of a split plan: _merge_pp may fold it into a SLIDE_OP_PP_STAGE launch)
-        self._emit(make_op(OP_GEMM, i=(rows, x_ld, ld, n_cob, npx_log2, in_bs, self.prec, cbw, glds | (2 if w_cm else 0) | (4 if has_pair else 0), knob),
-                           f=(-1.0 if self.persistent == 2 else float(os.environ.get('SLIDE_STAGGER_US', '0')),) + gf,
-                                p=(X.data_ptr(), Wd.data_ptr(), edp,
-                                   None if sc is None else sc.data_ptr() + 4 * aff_off,
-                                   None if sh is None else sh.data_ptr() + 4 * aff_off, None,
-                                   None if gn_fin is None else gn_fin.data_ptr(),
-                                   self._sched().data_ptr() if self.persistent else None,
-                                   None if gather is None else gtab.data_ptr(),
-                                   (None if pre_gather is None else pre_gather.data_ptr()) if gather is None
-                                   else gather[1].data_ptr(),
-                                   None if wfrag is None else wfrag.data_ptr(), None,
-                                   None if pair_tabs is None else pair_tabs[1].data_ptr(),
-                                   None if pair_tabs is None else pair_tabs[2].data_ptr())))
-        if pair_tabs is not None:  # PAIR_NBR residual: p[9] = neighbour table, p[12] / p[13] = squared distances / weights
-            assert gather is None and pre_gather is None
-            self.ops[-1].p[9] = pair_tabs[0].data_ptr()
-        self.flops += 2 * rows * sum(int(s["w"].size) for s in segs)
+        # (a per-point layer of a split plan: _merge_pp may fold it into a SLIDE_OP_PP_STAGE launch, from its float weights)
+        pp = (self.use_gxs and npx_log2 == 4 and gather is None and gn_fin is None and pre_gather is None and wfrag is None and
+              not any(v[1].get("pre_add") is not None for v in vec_list))
+        nbr, d2, wts = pair_tabs or (None, None, None)  # PAIR_NBR residual: p[9] = neighbour table, p[12] / p[13] = squared distances / weights
+        assert pair_tabs is None or (gather is None and pre_gather is None)
+        self.flops += fl
+        return self._emit(make_op(OP_GEMM, i=(rows, x_ld, ld, n_cob, npx_log2, in_bs, self.prec, cbw, glds | (2 if w_cm else 0) | (4 if has_pair else 0), knob),
+                                  f=(-1.0 if self.persistent == 2 else float(os.environ.get('SLIDE_STAGGER_US', '0')),) + gf,
+                                  p=(X.data_ptr(), Wd.data_ptr(), edp, None if sc is None else sc.data_ptr() + 4 * aff_off,
+                                     None if sh is None else sh.data_ptr() + 4 * aff_off, None, _dp(gn_fin),
+                                     self._sched().data_ptr() if self.persistent else None, _dp(gtab),
+                                     _dp(gather[1] if gather is not None else pre_gather if pair_tabs is None else nbr),
+                                     _dp(wfrag), None, _dp(d2), _dp(wts))),
+                          flops=fl, nbytes=(rd, wr), w16=W if pp else None)  # nbytes: algorithmic HBM bytes (read, written)
 
     @staticmethod
     def _split1_ok(*ws):
         """the single-accumulator split kernels (csrc/gemm_gxs.hip) scale the weight's high term by 2^11 in fp16: |w| < 32"""
         return all(float(np.abs(w).max()) < 31.0 for w in ws if w.size)
 
-    def _emit_gx(self, gx, npx_log2, rows, ld, n_cob, Wd, edp, segs, W, vec_list, in_affine, pair_tabs, chain=None, keep=None):
+    def _emit_gx(self, gx, npx_log2, rows, ld, n_cob, Wd, edp, segs, W, vec_list, in_affine, pair_tabs, chain=None):
         """SLIDE_OP_GEMM_GX (include/slide_engine.h): gx = dict(ta, tb (fp16 tables [B*16][t_ld]), coff (first table column),
         k_pad, rows, mode, add=(tensor, offset, per-sample stride, idx tensor or None, idx stride) or None, vv = per-sample
         (vd | vw) fp32 [B][2][t_ld] of the 8-neighbour samples or None); pair_tabs = (neighbour, d2, w tables) for those"""
@@ -450,13 +505,10 @@ class DenoiserEngine:
         assert ta.dtype == (torch.float16 if self.prec == 1 else torch.float32) and ta.shape == tb.shape and coff % 8 == 0
         assert ta.shape[1] >= coff + ld
         fl = 2 * rows * sum(int(s_["w"].size) for s_ in segs)
-        self.gemm_flops[len(self.ops)] = fl
         rd = 2 * (rows >> npx_log2) * 16 * ld * tes + W.size * tes
         wr = sum(rows * v[2] * v[1]["out"].element_size() for v in vec_list if v[1]["out"] is not None)
         if chain is not None:  # the chained layer's work rides on this launch
             fl += chain["flops"]; rd += chain["wbytes"]; wr += chain["wr"]
-            self.gemm_flops[len(self.ops)] = fl
-        self.gemm_bytes[len(self.ops)] = (rd, wr)
         sc = sh = None
         in_bs = aff_off = 0
         if in_affine is not None:
@@ -483,31 +535,29 @@ class DenoiserEngine:
         if n64 == 0:  # 128-channel tiles: two workgroups per CU (80 KB each)
             shm128 = lambda k_: k_ * (16384 + 4096 * nsamp) + (4 * 40 + 4 * 96) * 4 + nsamp * nvec * ld * 2 + 16
             nst = 3 if shm128(3) <= 80 * 1024 else 2
-        self.kernel_names[len(self.ops)] = "gemm_gx_%skernel<%d, %d, %d>" % (("", "n64_", "n64w_")[n64], npx_log2, nst, gx["mode"])
+        name = "gemm_gx_%skernel<%d, %d, %d>" % (("", "n64_", "n64w_")[n64], npx_log2, nst, gx["mode"])
         if self.prec == 2:  # split arithmetic on float tables: csrc/gemm_gxs.hip (256 x 64 tiles)
             if not self._split1_ok(W):
                 raise SlideHipError("a weight of magnitude >= 31 in a generated-X layer: the split pair-decomposition kernels scale the "
                                     "weights' high terms by 2^11 in fp16 -- build this plan with SLIDE_GXS=0")
             n64 = 3
-            self.kernel_names[len(self.ops)] = ("gemm_gxs_chain_kernel<%d>" % npx_log2) if chain is not None else \
+            name = ("gemm_gxs_chain_kernel<%d>" % npx_log2) if chain is not None else \
                 "gemm_gxs_kernel<%d, %d>" % (npx_log2, gx["mode"])
             assert chain is None or (npx_log2 == 8 and gx["mode"] == 0 and n_cob <= 2 and chain["k_pad"] == n_cob * 32)
-        self._emit(make_op(OP_GEMM_GX,
-                           i=(rows, ta.shape[1], ld, n_cob, npx_log2, in_bs, gx["mode"], 0 if add is None else add[2],
-                              0 if add is None else add[4], 0 if vv is None else 2 * vv.shape[2]),
-                           f=(float(n64),) + ((float(chain["n_cob"]), float(chain["k_pad"])) if chain is not None else ()),
-                           p=(ta.data_ptr() + tes * coff, Wd.data_ptr(), edp,
-                              None if sc is None else sc.data_ptr() + 4 * aff_off,
-                              None if sh is None else sh.data_ptr() + 4 * aff_off,
-                              tb.data_ptr() + tes * coff,
-                              None if add is None else add[0].data_ptr() + 4 * add[1],
-                              None if add is None or add[3] is None else add[3].data_ptr(),
-                              None if pair_tabs is None else pair_tabs[0].data_ptr(),
-                              None if pair_tabs is None else pair_tabs[1].data_ptr(),
-                              None if pair_tabs is None else pair_tabs[2].data_ptr(),
-                              None if vv is None else vv.data_ptr() + 4 * coff,
-                              None if chain is None else chain["W"].data_ptr(), None if chain is None else chain["epi_ptr"])))
         self.flops += fl
+        return self._emit(make_op(OP_GEMM_GX,
+                                  i=(rows, ta.shape[1], ld, n_cob, npx_log2, in_bs, gx["mode"], 0 if add is None else add[2],
+                                     0 if add is None else add[4], 0 if vv is None else 2 * vv.shape[2]),
+                                  f=(float(n64),) + ((float(chain["n_cob"]), float(chain["k_pad"])) if chain is not None else ()),
+                                  p=(ta.data_ptr() + tes * coff, Wd.data_ptr(), edp,
+                                     None if sc is None else sc.data_ptr() + 4 * aff_off,
+                                     None if sh is None else sh.data_ptr() + 4 * aff_off,
+                                     tb.data_ptr() + tes * coff,
+                                     None if add is None else add[0].data_ptr() + 4 * add[1],
+                                     None if add is None else _dp(add[3])) + tuple(_dp(t) for t in pair_tabs or (None,) * 3) +
+                                    (None if vv is None else vv.data_ptr() + 4 * coff,
+                                     None if chain is None else chain["W"].data_ptr(), None if chain is None else chain["epi_ptr"])),
+                          flops=fl, nbytes=(rd, wr), name=name)
 
     # ------------------------------------------------------------------ blocks
     def _mlp_segments(self, pfx, tvec, cvec, out1, res_out):
@@ -554,16 +604,17 @@ class DenoiserEngine:
             seg["addvec"] = (cvec, self._cvec_off(pfx + ".fc_condition", c2), self._c_bs, None, 0)
         if has_rest and pair is not None and self._sa_chain(pfx, npx_log2, pair, cvec, seg, final_out, final_coff):
             return
-        if (has_rest and pair is not None and self.use_gxs and npx_log2 == 8 and ru(gn_layout(c2)[1]) <= 64
-                and os.environ.get("SLIDE_GXS_CHAIN", "1") != "0"):
-            # split plans (round 5): second_mlp -> rest_mlp of an SA block in ONE launch -- h2 stays in the generated-X kernel's
-            # accumulators and feeds rest_mlp's contraction from there (csrc/gemm_gxs.hip, CHAIN); needs every channel of h2 in
-            # one 64-channel tile.  SLIDE_GXS_CHAIN=0: two launches and an h2 round trip
+        if has_rest:
             c3 = sd[pfx + ".rest_mlp.0.weight"].shape[0]
             assert np.array_equal(gn_layout(c2)[0], np.arange(c2)), "second_mlp width with padded GroupNorm groups"
             seg3 = with_res(dict(w=self._w(pfx + ".rest_mlp.0.weight"), bias=sd[pfx + ".rest_mlp.0.bias"], mode=EPI_NORM,
                                  flags=F_POST_RELU, layout=gn_layout(c3), out=final_out, out_coff=final_coff,
                                  gn=(sd[pfx + ".rest_mlp.1.group_norm.weight"], sd[pfx + ".rest_mlp.1.group_norm.bias"])))
+        if (has_rest and pair is not None and self.use_gxs and npx_log2 == 8 and ru(gn_layout(c2)[1]) <= 64
+                and os.environ.get("SLIDE_GXS_CHAIN", "1") != "0"):
+            # split plans (round 5): second_mlp -> rest_mlp of an SA block in ONE launch -- h2 stays in the generated-X kernel's
+            # accumulators and feeds rest_mlp's contraction from there (csrc/gemm_gxs.hip, CHAIN); needs every channel of h2 in
+            # one 64-channel tile.  SLIDE_GXS_CHAIN=0: two launches and an h2 round trip
             if self._split1_ok(seg3["w"]):
                 layer2 = self._gemm(None, npx_log2, [seg3], pair_tabs=pair["tabs"], defer=dict(rows=rows, k_pad=ru(c2)))
                 seg["out"] = None
@@ -576,11 +627,6 @@ class DenoiserEngine:
             h2 = self._buf(rows, c2, cm=npx_log2 >= 7)
             seg["out"] = h2
             first_gemm(seg)
-            c3 = sd[pfx + ".rest_mlp.0.weight"].shape[0]
-            assert np.array_equal(gn_layout(c2)[0], np.arange(c2)), "second_mlp width with padded GroupNorm groups"
-            seg3 = with_res(dict(w=self._w(pfx + ".rest_mlp.0.weight"), bias=sd[pfx + ".rest_mlp.0.bias"], mode=EPI_NORM,
-                                 flags=F_POST_RELU, layout=gn_layout(c3), out=final_out, out_coff=final_coff,
-                                 gn=(sd[pfx + ".rest_mlp.1.group_norm.weight"], sd[pfx + ".rest_mlp.1.group_norm.bias"])))
             self._gemm(h2, npx_log2, [seg3], pair_tabs=None if pair is None else pair["tabs"])
         else:
             with_res(seg)
@@ -625,10 +671,7 @@ class DenoiserEngine:
         ta, tb = pair["ta"], pair["tb"]
         rows = B * 256
         fl = 2 * rows * (w1.size + w2.size)
-        self.gemm_flops[len(self.ops)] = fl
-        self.gemm_bytes[len(self.ops)] = (2 * B * 16 * (c1 + c3) * 2 + (w1.size + w2.size) * 2, rows * c3 * 2)
         self.flops += fl
-        self.kernel_names[len(self.ops)] = "sa_chain_kernel<%d>" % (c2 // 32)
         self._emit(make_op(OP_SA_CHAIN,
                            i=(B, ta.shape[1], c1, c2, c3, l2[3], l3[3], 0 if add0 is None else add0[4], 0 if add0 is None else add0[2],
                               0 if add1 is None else add1[2]),
@@ -638,7 +681,9 @@ class DenoiserEngine:
                               d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
                               None if add0 is None else add0[0].data_ptr() + 4 * add0[1],
                               None if add0 is None or add0[3] is None else add0[3].data_ptr(),
-                              None if add1 is None else add1[0].data_ptr() + 4 * add1[1], final_out.data_ptr())))
+                              None if add1 is None else add1[0].data_ptr() + 4 * add1[1], final_out.data_ptr())),
+                   flops=fl, nbytes=(2 * B * 16 * (c1 + c3) * 2 + (w1.size + w2.size) * 2, rows * c3 * 2),
+                   name="sa_chain_kernel<%d>" % (c2 // 32))
         return True
 
     def _attention_query(self, apfx, K):
@@ -725,13 +770,13 @@ class DenoiserEngine:
         # loop-invariant when the coordinates are a fixed condition?  No: y changes every step.
         v2 = ldy <= 2048 and (os.environ.get("SLIDE_PAIR_NORM_V2", "0") != "0" or self.prec != 1)
         assert (fin is None or v2) and (self.prec == 1 or v2)
-        self.kernel_names[len(self.ops)] = "pair_norm2_kernel<%s, %s>" % ("true" if fp else "false", "_Float16" if self.prec == 1 else "float")
         self._emit(make_op(OP_PAIR_NORM, i=(B, ldy, K, 2 if v2 else 1, int(self.prec != 1)),
                            p=(Y.data_ptr(), self.xyz.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), ed.data_ptr(),
                               ta.data_ptr(), tb.data_ptr(), self.kidx.data_ptr() if fp else None,
                               self.kd2.data_ptr() if fp else None, self.kw.data_ptr() if fp else None,
                               d[2].data_ptr() if fp else None, vv.data_ptr() if fp else None,
-                              None if fin is None else fin.data_ptr())))
+                              _dp(fin))),
+                   name="pair_norm2_kernel<%s, %s>" % ("true" if fp else "false", "_Float16" if self.prec == 1 else "float"))
         return dict(ta=ta, tb=tb, vv=vv, offs=offs, ldy=ldy, rows=B * 16 * K, vv_in=vv_in,
                     tabs=(self.kidx, self.kd2, self.kw) if fp else None)
 
@@ -920,14 +965,12 @@ class DenoiserEngine:
         a.slots, a.n_slots = sd_.data_ptr(), len(slots)
         self.A.keep.append((a, keep))  # the op carries a HOST pointer to the argument block
         rows = B * 16 * K
-        self.gemm_flops[len(self.ops)] = 2 * rows * fl
-        self.gemm_bytes[len(self.ops)] = (2 * B * 16 * ta.shape[1] * 2, B * 16 * cout * 2)
         self.flops += 2 * rows * fl
-        self._tail_of[out.data_ptr()] = len(self.ops)
-        self._body_args[len(self.ops)] = a
-        self.kernel_names[len(self.ops)] = "block_body_kernel<%d, %s, %d, %d, %d>" % (
-            npx_log2, "true" if rest else "false", (c2 // 32) if rest else 0, n_mo // 32, n_u // 32)
-        self._emit(make_op(OP_BLOCK_BODY, i=(npx_log2, int(rest)), p=(ctypes.addressof(a),)))
+        self._tail_of[out.data_ptr()] = self._emit(
+            make_op(OP_BLOCK_BODY, i=(npx_log2, int(rest)), p=(ctypes.addressof(a),)), body=a,
+            flops=2 * rows * fl, nbytes=(2 * B * 16 * ta.shape[1] * 2, B * 16 * cout * 2),
+            name="block_body_kernel<%d, %s, %d, %d, %d>" % (npx_log2, "true" if rest else "false", (c2 // 32) if rest else 0,
+                                                            n_mo // 32, n_u // 32))
 
     def _attention(self, apfx, npx_log2, K, g, q_in, mo, mlp_first, mlp_res, out, out_ld_buf, gather=None, qctx=None,
                    extra_q=(), pair=None, body=None):
@@ -1114,18 +1157,14 @@ class DenoiserEngine:
                 cmw = (lambda w: np.ascontiguousarray(w.reshape(w.shape[0], -1, 32).transpose(1, 0, 2))) if self.use_cm else (lambda w: w)
                 wdt = torch.float16 if self.prec == 1 else torch.float32  # (split tail: float row-major weights)
                 d = [self.A.put(cmw(w5), wdt), self.A.put(cmw(wv), wdt), self.A.put(vec)]
-                if self.prec != 1:
-                    self.kernel_names[len(self.ops)] = "attn_tail_split_kernel<%d>" % npx_log2
                 assert out.dtype == self.adt and u.dtype == self.adt and mo.dtype == self.adt and not self._is_cm(out)
                 assert self._is_fm(u) == self._is_fm(mo)
                 self._sync(1, 0)
                 self.flops += 2 * rows * (w5.size + wv.size)
-                self.gemm_flops[len(self.ops)] = 2 * rows * cout * (len(lay[0]) + wv_l.shape[1])  # logical channels
                 out_cm = None
                 if self.use_cm and os.environ.get("SLIDE_CM_TABLES", "0") != "0" and npx_log2 == 8:  # (SA outputs feed gathers)
                     out_cm = self._cm_copy[out.data_ptr()] = self.A.zeros(out.shape[0], out.shape[1], dtype=self.adt)
-                self._tail_of[out.data_ptr()] = len(self.ops)
-                self._emit(make_op(OP_ATTN_TAIL, i=(rows, self._ldp(u), u.shape[1], self._ldp(mo), mo.shape[1], Cp // 32, npx_log2,
+                self._tail_of[out.data_ptr()] = self._emit(make_op(OP_ATTN_TAIL, i=(rows, self._ldp(u), u.shape[1], self._ldp(mo), mo.shape[1], Cp // 32, npx_log2,
                                                     vlay[3], vlay[2], out.shape[1]),
                                         # f[1]: 1 = chunk-major operands, + 2 = two-stage ring at three workgroups per CU (opt-in,
                                         # SLIDE_TAIL_OCC3=1: measured neutral, 373.0 vs 372.3 shapes/s)
@@ -1134,7 +1173,9 @@ class DenoiserEngine:
                                            (4.0 if (Cp // 32) % 4 == 0 and Cp // 32 >= int(os.environ.get("SLIDE_TAIL_WIDE", "1000")) else 0.0) +
                                            (16.0 if self._is_fm(mo) else 0.0)),  # bit 4: u / mo fragment-major
                                         p=(u.data_ptr(), d[0].data_ptr(), mo.data_ptr(), d[1].data_ptr(), out.data_ptr(),
-                                           d[2].data_ptr(), None if out_cm is None else out_cm.data_ptr())))
+                                           d[2].data_ptr(), _dp(out_cm))),
+                    flops=2 * rows * cout * (len(lay[0]) + wv_l.shape[1]),  # logical channels
+                    name=None if self.prec == 1 else "attn_tail_split_kernel<%d>" % npx_log2)
                 return
             # lane 0 (value branch), then the join
             V = self._buf(rows, cout)
@@ -1163,9 +1204,9 @@ class DenoiserEngine:
         ptrs = (self.xyz.data_ptr(), feat_in.data_ptr(), self.kidx.data_ptr())
         if kind == OP_ASSEMBLE_FP:
             ptrs += (self.kd2.data_ptr(),)
-        if nsplit and c_begin == C:  # only coordinate channels left: loop-invariant when the coordinates are a fixed condition
-            self.xyz_copy_idx.append(len(self.ops))
-        self._emit(make_op(kind, i=(B, C, feat_in.shape[1], ldg, K, self.prec, c_begin, ldg - c_begin), p=ptrs + (g.data_ptr(),)))
+        # only coordinate channels left: loop-invariant when the coordinates are a fixed condition
+        self._emit(make_op(kind, i=(B, C, feat_in.shape[1], ldg, K, self.prec, c_begin, ldg - c_begin), p=ptrs + (g.data_ptr(),)),
+                   role="xyz_copy" if nsplit and c_begin == C else None)
         return g, ((feat_in, self.kidx, K, nsplit) if nsplit else None), rows
 
     def _sa_module(self, i, feat_in, C, extra_q=()):
@@ -1237,14 +1278,14 @@ class DenoiserEngine:
         self._lane = 1
         # skip-feature columns: written by the producer of U itself where it can (the point preparation for the input
         # features, the fused attention tail of the SA block that made U) -- a COPY launch otherwise
-        tail_idx = self._tail_of.get(U.data_ptr())
+        tail = self._tail_of.get(U.data_ptr())  # the launch that wrote U, if it is a fused tail / block body
         if self.fold_copies and U is self.feat0:
             self._prep_copies.append((Z.data_ptr() + es * c_last, Z.shape[1], 0, CU))
-        elif self.fold_copies and tail_idx is not None and tail_idx in self._body_args:
-            ba = self._body_args[tail_idx]
+        elif self.fold_copies and tail is not None and tail.body is not None:
+            ba = tail.body
             ba.out2, ba.out2_ld, ba.out2_n = Z.data_ptr() + es * c_last, Z.shape[1], CU
-        elif self.fold_copies and tail_idx is not None:
-            t_op = self.ops[tail_idx]
+        elif self.fold_copies and tail is not None:
+            t_op = tail.op
             t_op.p[7], t_op.f[2], t_op.f[3] = Z.data_ptr() + es * c_last, float(Z.shape[1]), float(CU)
         else:
             self._emit(make_op(OP_COPY_COLS, i=(B * 16, CU, U.shape[1], Z.shape[1], int(self.prec == 1), int(self.prec == 1)),
@@ -1252,9 +1293,9 @@ class DenoiserEngine:
         if self.fold_copies:
             self._prep_copies.append((Z.data_ptr() + es * (c_last + CU), Z.shape[1], 1, 3))
         else:
-            self.xyz_copy_idx.append(len(self.ops))  # loop-invariant when the coordinates are a fixed condition
             self._emit(make_op(OP_COPY_COLS, i=(B * 16, 3, 3, Z.shape[1], 0, int(self.prec == 1)),
-                                    p=(self.xyz.data_ptr(), Z.data_ptr() + es * (c_last + CU))))
+                               p=(self.xyz.data_ptr(), Z.data_ptr() + es * (c_last + CU))),
+                       role="xyz_copy")  # loop-invariant when the coordinates are a fixed condition
         self._lane = 0
         if body is not None:
             self._emit_block_body(body, m1, 7, K, Z, self.cvec)
@@ -1265,22 +1306,15 @@ class DenoiserEngine:
         n2 = sd[m2 + ".res_connect.weight"].shape[0]
         hz, rz = self._buf(B * 16, n1), self._buf(B * 16, n2)
         f2, r2 = self._mlp_segments(m2, self.tvec, self.cvec, hz, rz)
-        i0 = len(self.ops)
+        i0 = len(self.plan)
         self._gemm(Z, 4, [f2, r2])
         out = out_buf if out_buf is not None else self._buf(B * 16, n2)
         self._mlp_tail(m2, 4, hz, self.cvec, rz, out)
         if out_buf is not None:  # the last FP block: its second Mlp may join the output head in one launch (_point_chain)
-            self._chain_front = dict(idx=list(range(i0, len(self.ops))), Z=Z, zin=zin, m2=m2, n1=n1, n2=n2)
+            self._chain_front = dict(launches=self.plan[i0:], Z=Z, zin=zin, m2=m2, n1=n1, n2=n2)
         return out, n2
 
-    def _remap_point_chain(self, remap):
-        pc = getattr(self, "point_chain", None)
-        if pc is not None:
-            pc["idx"] = [remap[q] for q in pc["idx"]]
-            if len(set(pc["idx"])) != 4 or pc["idx"] != list(range(pc["idx"][0], pc["idx"][0] + 4)):
-                self.point_chain = None  # (its launches went into another merged launch)
-
-    def _point_chain(self, dec0, head_i0, w0, w1, lay0):
+    def _point_chain(self, dec0, head, w0, w1, lay0):
         """round 5: the last FP block's second Mlp + the output head as ONE launch (SLIDE_OP_POINT_CHAIN, csrc/point_chain.hip) -- what
         the kernel needs, or None when the shapes are outside what it covers (fp16 plans; every width 128 with identity GroupNorm layout;
         per-timestep t-embedding table).  The samplers swap it in for the four per-point GEMM launches (diffusion.py); the plan itself
@@ -1293,7 +1327,7 @@ class DenoiserEngine:
         c2 = sd[m2 + ".second_mlp.0.weight"].shape[0]
         has_t, has_c = (m2 + ".fc.weight") in sd, (m2 + ".fc_condition.weight") in sd
         if not (fr["n1"] == 128 and fr["n2"] == 128 and c2 == 128 and (m2 + ".rest_mlp.0.weight") not in sd and ident(128)
-                and len(fr["idx"]) == 2 and fr["idx"][1] + 1 == head_i0 and fr["Z"].shape[1] <= 192 and w0.shape[0] == 128
+                and len(fr["launches"]) == 2 and self.plan[-4:] == fr["launches"] + head and fr["Z"].shape[1] <= 192 and w0.shape[0] == 128
                 and np.array_equal(lay0[0], np.arange(128)) and lay0[3] == 4 and lay0[2] == 128 and 128 < dec0.shape[1] <= 160
                 and w1.shape[1] == 128 and self.out_dim <= 64 and sd["fc_lyaer.1.weight"].shape[0] == 128):
             return None
@@ -1313,7 +1347,9 @@ class DenoiserEngine:
         v0 = np.stack([sd["fc_lyaer.0.bias"], sd["fc_lyaer.1.weight"], sd["fc_lyaer.1.bias"]]).astype(np.float32)
         off = lambda lst, pfx: sum(w for _, w in lst[:[p_ for p_, _ in lst].index(pfx)])
         W2 = self._w(m2 + ".second_mlp.0.weight")
-        d = dict(idx=fr["idx"] + [head_i0, head_i0 + 1], Z=fr["Z"], kz=kz, X=dec0, k0=dec0.shape[1], n1c=n1c,
+        for role, e in zip(("pc0", "pc1", "pc2", "pc3"), self.plan[-4:]):
+            e.roles.add(role)
+        d = dict(Z=fr["Z"], kz=kz, X=dec0, k0=dec0.shape[1], n1c=n1c,
                  Wz=A.put(Wz, torch.float16), W2=A.put(W2, torch.float16),
                  W0=A.put(W0, torch.float16), W1=A.put(W1, torch.float16), vz=A.put(vz), v2=A.put(v2), v0=A.put(v0), b1=A.put(b1),
                  t_off=off(self._tvec, m2 + ".fc") if has_t else None,
@@ -1356,11 +1392,6 @@ class DenoiserEngine:
     def _build(self):
         hp, sd, B, A = self.hp, self.sd, self.B, self.A
         arch = hp["architecture"]
-        self.flops = 0
-        self.gemm_flops = {}
-        self.gemm_bytes = {}
-        self.kernel_names = {}  # rocprofv3 kernel name of the round-3 ops (bench.py's roofline attribution), by op index
-        self.xyz_copy_idx = []
         self.persistent = int(os.environ.get('SLIDE_PERSISTENT', '0'))  # 1: tile counter per XCD, 2: static tile lists
         # persistent I/O + per-step state
         self.x = A.zeros(B, 16, self.cx)
@@ -1383,8 +1414,8 @@ class DenoiserEngine:
         self.cvec = A.zeros(B, n_fcc)
         temb_slot = None
         if self.per_sample_t:
-            temb_slot = len(self.ops)
-            self.ops.append(None)  # TEMB placeholder (needs the .fc order of the walk)
+            temb_slot = Launch(None)  # TEMB placeholder (needs the .fc order of the walk)
+            self.plan.append(temb_slot)
         # (opt-in, SLIDE_CM_TABLES=1: chunk-major second copies of the per-point tables the first layers gather from, written
         # by prep_points / the attention tails -- measured neutral, 298-301 shapes/s either way: the gathers hit the vector cache)
         feat0_cm = None
@@ -1392,13 +1423,10 @@ class DenoiserEngine:
             feat0_cm = self._cm_copy[self.feat0.data_ptr()] = self._buf(B * 16, C0)
         # COPY launches folded into the producers of their sources (SLIDE_FOLD_COPIES=0: separate launches)
         self.fold_copies = os.environ.get("SLIDE_FOLD_COPIES", "1") != "0"
-        self._prep_copies, self._tail_of = [], {}
-        self._body_args = {}
-        self._prep_idx = len(self.ops)
-        self._emit(make_op(OP_PREP_POINTS, i=(B, self.cx, self.feat0.shape[1], self.prec),
-                                p=(self.x.data_ptr(), self.xyz.data_ptr(), self.feat0.data_ptr(), self.kidx.data_ptr(),
-                                   self.kd2.data_ptr(), None if feat0_cm is None else feat0_cm.data_ptr(), None,
-                                   self.kw.data_ptr())))
+        self._prep_copies, self._tail_of = [], {}  # _tail_of: output table (data_ptr) -> the fused tail / block body that writes it
+        prep = self._emit(make_op(OP_PREP_POINTS, i=(B, self.cx, self.feat0.shape[1], self.prec),
+                                  p=(self.x.data_ptr(), self.xyz.data_ptr(), self.feat0.data_ptr(), self.kidx.data_ptr(),
+                                     self.kd2.data_ptr(), _dp(feat0_cm), None, self.kw.data_ptr())), role="prep").op
         feats, chans = [self.feat0], [C0]
         nsa, nfp = len(arch["npoint"]), len(arch["decoder_feature_dim"]) - 1
         # FP block j takes feats[nsa + j - nfp] as its skip / query input -- the table SA block nsa + j - nfp reads as well:
@@ -1430,17 +1458,16 @@ class DenoiserEngine:
         if self.fold_copies:
             self._prep_copies.append((dec0.data_ptr() + dec0.element_size() * c, dec0.shape[1], 1, 3))
         else:
-            self.xyz_copy_idx.append(len(self.ops))
             self._emit(make_op(OP_COPY_COLS, i=(B * 16, 3, 3, dec0.shape[1], 0, int(self.prec == 1)),
-                                    p=(self.xyz.data_ptr(), dec0.data_ptr() + dec0.element_size() * c)))
+                               p=(self.xyz.data_ptr(), dec0.data_ptr() + dec0.element_size() * c)), role="xyz_copy")
         hh = self._buf(B * 16, sd["fc_lyaer.0.weight"].shape[0])
         assert sd["fc_lyaer.0.weight"].shape[1] == c + 3
-        head_i0 = len(self.ops)
-        self._gemm(dec0, 4, [dict(w=self._w("fc_lyaer.0.weight"), bias=sd["fc_lyaer.0.bias"], mode=EPI_NORM,
+        head = [None, None]
+        head[0] = self._gemm(dec0, 4, [dict(w=self._w("fc_lyaer.0.weight"), bias=sd["fc_lyaer.0.bias"], mode=EPI_NORM,
                                   flags=F_POST_RELU, layout=gn_layout(sd["fc_lyaer.0.weight"].shape[0]), out=hh,
                                   gn=(sd["fc_lyaer.1.weight"], sd["fc_lyaer.1.bias"]))])
         self.eps_pad = self._buf(B * 16, self.out_dim, dtype=torch.float32)
-        self._gemm(hh, 4, [dict(w=self._w("fc_lyaer.3.weight"), bias=sd["fc_lyaer.3.bias"], mode=EPI_RAW, out=self.eps_pad)])
+        head[1] = self._gemm(hh, 4, [dict(w=self._w("fc_lyaer.3.weight"), bias=sd["fc_lyaer.3.bias"], mode=EPI_RAW, out=self.eps_pad)])
         # what SLIDE_OP_HEAD_UPDATE needs (the samplers replace the two head GEMMs + their update launch by it, diffusion.py)
         self.head = None
         w0, w1 = self._w("fc_lyaer.0.weight"), self._w("fc_lyaer.3.weight")
@@ -1452,13 +1479,13 @@ class DenoiserEngine:
             W1 = np.zeros((n1c * 32, 128), np.float32); W1[:w1.shape[0]] = w1
             b1 = np.zeros(n1c * 32, np.float32); b1[:w1.shape[0]] = sd["fc_lyaer.3.bias"]
             v0 = np.stack([sd["fc_lyaer.0.bias"], sd["fc_lyaer.1.weight"], sd["fc_lyaer.1.bias"]]).astype(np.float32)
-            self.head = dict(idx=[head_i0, head_i0 + 1], X=dec0, k0=dec0.shape[1], n1c=n1c,
+            head[0].roles.add("head0"); head[1].roles.add("head1")
+            self.head = dict(X=dec0, k0=dec0.shape[1], n1c=n1c,
                              W0=self.A.put(W0, torch.float16), W1=self.A.put(W1, torch.float16), v0=self.A.put(v0), b1=self.A.put(b1))
-        self.point_chain = self._point_chain(dec0, head_i0, w0, w1, lay0)
+        self.point_chain = self._point_chain(dec0, head, w0, w1, lay0)
         self.eps = A.zeros(B, 16, self.out_dim)
-        self.eps_copy_idx = len(self.ops)  # samplers read eps_pad directly and drop this op
         self._emit(make_op(OP_COPY_COLS, i=(B * 16, self.out_dim, self.eps_pad.shape[1], self.out_dim, 0, 0),
-                                p=(self.eps_pad.data_ptr(), self.eps.data_ptr())))
+                           p=(self.eps_pad.data_ptr(), self.eps.data_ptr())), role="eps_copy")  # samplers read eps_pad and drop this op
         # t-embedding MLP + all .fc layers, class embedding + all .fc_condition layers (input-major weights)
         assert sum(w for _, w in self._tvec) == n_fc and sum(w for _, w in self._cvec) == n_fcc
         half = self.t_dim // 2
@@ -1477,7 +1504,7 @@ class DenoiserEngine:
                           d[3].data_ptr(), d[4].data_ptr(), d[5].data_ptr(), self.tvec.data_ptr(), d[6].data_ptr()))
         self.table_ops = None
         if self.per_sample_t:
-            self.ops[temb_slot] = temb
+            temb_slot.op = temb
         else:
             self.table_ops = (SlideOp * 1)(temb)
         wc = np.concatenate([sd[p + ".weight"] for p, _ in self._cvec], axis=0)
@@ -1491,184 +1518,48 @@ class DenoiserEngine:
             for q, (dst, ld_, kind, n_) in enumerate(self._prep_copies):
                 tab[q].dst, tab[q].ld, tab[q].kind, tab[q].n = dst, ld_, kind, n_
             self._prep_tab = A.put(np.frombuffer(bytes(tab), dtype=np.uint8).copy())
-            prep = self.ops[self._prep_idx]
             prep.p[6], prep.i[4] = self._prep_tab.data_ptr(), len(self._prep_copies)
-        self._merge_chains()
-        self._merge_gx_pairs()
-        self._merge_chain_query()
-        self._merge_pp()
-        self._w16 = {}
+        # (the host blocks the merged ops point to are kept alive here)
+        self._chain_keep, self._dual_keep, self._chain_p_keep, self._pp_keep = [], [], [], []
+        for merge in (self._merge_chains, self._merge_gx_pairs, self._merge_chain_query, self._merge_pp):
+            self.plan = rewrite(self.plan, merge())
+        self._derive_tables()
         # forward() runs the point chain too (round 6): what the samplers' step plans launch is what the golden forwards measure
         self.layer_ops = list(self.ops)  # (the four per-point GEMMs as launches of their own: parity tests of the layers)
         ops = self.layer_ops
         self._fwd_chain_args = self.point_chain_args()
-        if self._fwd_chain_args is not None and all(self.ops[i] is not None and self.ops[i].kind == OP_GEMM for i in self.point_chain["idx"]):
+        if self._fwd_chain_args is not None and all(self.ops[i].kind == OP_GEMM for i in self.point_chain["idx"]):
             idx = self.point_chain["idx"]
             ops = [o if i != idx[0] else make_op(OP_POINT_CHAIN, p=(ctypes.addressof(self._fwd_chain_args),))
                    for i, o in enumerate(self.ops) if i not in idx[1:]]
         self.step_ops = (SlideOp * len(ops))(*ops)
         self.cond_ops = (SlideOp * 1)(self.cond_op)
 
-    def _merge_chain_query(self):
-        """SA blocks: [per-point query GEMM P | keys -> u GEMM (needs P) | fused Mlp chain (needs neither)] becomes
-        [chain + query GEMM in ONE launch (SLIDE_OP_SA_CHAIN_P) | keys -> u GEMM]: the query GEMM's launch and gap disappear under
-        the chain (SLIDE_CHAIN_P=0: three launches).  Op-index tables are re-keyed (the triple keeps its position)."""
-        if os.environ.get("SLIDE_CHAIN_P", "1") == "0":
-            return
-        is_p = lambda o: (o is not None and o.kind == OP_GEMM and o.i[4] == 4 and o.i[6] == 1 and not (o.i[8] & 6) and o.i[9] != 3 and o.p[3] and o.p[6]
-                          and not any(o.p[k] for k in (8, 9, 10, 11, 12, 13)))
-        new_ops, remap, i = [], {}, 0
-        self._chain_p_keep = []
-        flops, nbytes, names = {}, {}, {}
-        take = lambda src, dst, a_, b_: dst.__setitem__(b_, src[a_]) if a_ in src else None
-        while i < len(self.ops):
-            o0 = self.ops[i]
-            o1 = self.ops[i + 1] if i + 1 < len(self.ops) else None
-            o2 = self.ops[i + 2] if i + 2 < len(self.ops) else None
-            k = len(new_ops)
-            if (is_p(o0) and o1 is not None and o2 is not None and o1.kind == OP_GEMM_GX and o1.i[6] == 1 and o2.kind == OP_SA_CHAIN
-                    and o0.i[0] == o2.i[0] * 16 and o0.i[10] == o1.i[10] == o2.i[10]):
-                pair = (SlideOp * 2)(SlideOp.from_buffer_copy(bytes(o2)), SlideOp.from_buffer_copy(bytes(o0)))
-                self._chain_p_keep.append(pair)
-                op = make_op(OP_SA_CHAIN_P, i=(o2.i[0],), p=(ctypes.addressof(pair),))
-                op.i[10] = o0.i[10]
-                new_ops += [op, o1]
-                remap[i], remap[i + 2], remap[i + 1] = k, k, k + 1
-                flops[k] = self.gemm_flops.get(i, 0) + self.gemm_flops.get(i + 2, 0)
-                nbytes[k] = tuple(self.gemm_bytes.get(i, (0, 0))[z] + self.gemm_bytes.get(i + 2, (0, 0))[z] for z in (0, 1))
-                names[k] = "sa_chain_p_kernel<%d>" % (o2.i[3] // 32)
-                for src, dst in ((self.gemm_flops, flops), (self.gemm_bytes, nbytes), (self.kernel_names, names)):
-                    take(src, dst, i + 1, k + 1)
-                i += 3
-                continue
-            new_ops.append(o0)
-            remap[i] = k
-            for src, dst in ((self.gemm_flops, flops), (self.gemm_bytes, nbytes), (self.kernel_names, names)):
-                take(src, dst, i, k)
-            i += 1
-        self.ops = new_ops
-        self.gemm_flops, self.gemm_bytes, self.kernel_names = flops, nbytes, names
-        self.xyz_copy_idx = [remap[q] for q in self.xyz_copy_idx]
-        self.eps_copy_idx = remap[self.eps_copy_idx]
-        self._prep_idx = remap[self._prep_idx]
-        self._remap_point_chain(remap)
-        if self.head is not None:
-            self.head["idx"] = [remap[q] for q in self.head["idx"]]
-        self._body_args = {remap[q]: v for q, v in self._body_args.items()}
-        self._tail_of = {k_: remap[v] for k_, v in self._tail_of.items()}
+    def _derive_tables(self):
+        """the finished plan as the rest of the code reads it, by position (plan_tables)"""
+        t = plan_tables(self.plan)
+        for k_ in ("gemm_flops", "gemm_bytes", "kernel_names", "xyz_copy_idx", "eps_copy_idx"):
+            setattr(self, k_, t[k_])
+        self._prep_idx = t["prep_idx"]
+        for e in self.plan:
+            e.w16 = None
+        for k_ in ("head", "point_chain"):  # (None where a merge pass took their launches)
+            if getattr(self, k_) is not None:
+                setattr(self, k_, None if t[k_] is None else dict(getattr(self, k_), idx=t[k_]))
 
-    def _merge_pp(self):
-        """split plans (round 5): runs of consecutive per-point launches -- 16-row SLIDE_OP_GEMM in the split arithmetic and the float
-        pair-table pass -- become ONE SLIDE_OP_PP_STAGE launch each (csrc/gemm_gxs.hip: one workgroup per sample walks the steps, the
-        dense layers as exact fp32 FMA chains; 30 -> 17 launches per position step).  SLIDE_PP=0 keeps the launches apart.
-        Op-index tables are re-keyed."""
-        # OPT-IN (SLIDE_PP=1): measured SLOWER -- one workgroup per sample re-reads every layer's weights per sample and its K loop is a
-        # chain of dependent L2 round trips on four waves: 55 - 131 us per stage launch against 27 - 45 us for the launches it replaces
-        # (position chain alone 365 -> 652 us per step, bench 379 -> 227 shapes/s)
-        if not self.use_gxs or os.environ.get("SLIDE_PP", "0") == "0":
-            return
-        B = self.B
-
-        def step_of(o):
-            if o is None:
-                return None
-            if o.kind == OP_GEMM and id(o) in self._w16 and o.i[0] == B * 16 and o.i[2] <= 192 and not o.i[10]:
-                W = self._w16[id(o)][1]
-                wt = self.A.put(np.ascontiguousarray(W.T), torch.float32)  # K-major [k_pad][n_cob*32]
-                return [0, o.p[0], wt.data_ptr(), o.p[2] & ~1, o.p[3] or 0, o.p[4] or 0, o.i[1], o.i[2], o.i[3], o.i[5]] + [0] * 6
-            if o.kind == OP_PAIR_NORM and o.i[3] == 2 and o.i[4] == 1 and o.i[0] == B and not o.i[10]:
-                return [1] + [o.p[k] or 0 for k in range(13)] + [o.i[1], o.i[2]]
-            return None
-        new_ops, remap, i = [], {}, 0
-        self._pp_keep = []
-        flops, nbytes, names = {}, {}, {}
-        while i < len(self.ops):
-            run, j = [], i
-            while j < len(self.ops) and len(run) < 8:
-                st = step_of(self.ops[j])
-                if st is None or (st[0] == 1 and sum(1 for r_ in run if r_[0] == 1) >= 2):
-                    break
-                run.append(st)
-                j += 1
-            k = len(new_ops)
-            if len(run) >= 2:
-                rec = np.array([len(run), B] + [v for st in run for v in st], np.int64)
-                self._pp_keep.append(rec)
-                op = make_op(OP_PP_STAGE, i=(B, len(run)), p=(rec.ctypes.data,))
-                new_ops.append(op)
-                for q in range(i, j):
-                    remap[q] = k
-                flops[k] = sum(self.gemm_flops.get(q, 0) for q in range(i, j))
-                nbytes[k] = tuple(sum(self.gemm_bytes.get(q, (0, 0))[z] for q in range(i, j)) for z in (0, 1))
-                names[k] = "pp_stage_kernel"
-                i = j
-                continue
-            new_ops.append(self.ops[i])
-            remap[i] = k
-            for src, dst in ((self.gemm_flops, flops), (self.gemm_bytes, nbytes), (self.kernel_names, names)):
-                if i in src:
-                    dst[k] = src[i]
-            i += 1
-        self.ops = new_ops
-        self.gemm_flops, self.gemm_bytes, self.kernel_names = flops, nbytes, names
-        self.xyz_copy_idx = [remap[q] for q in self.xyz_copy_idx]
-        self.eps_copy_idx = remap[self.eps_copy_idx]
-        self._prep_idx = remap[self._prep_idx]
-        self._remap_point_chain(remap)
-        if self.head is not None:
-            self.head["idx"] = [remap[q] for q in self.head["idx"]]
-            if len(set(self.head["idx"])) != 2:
-                self.head = None
-        self._body_args = {remap[q]: v for q, v in self._body_args.items()}
-        self._tail_of = {k_: remap[v] for k_, v in self._tail_of.items()}
-
-    def _merge_gx_pairs(self):
-        """the mode-1 (keys -> u) and mode-0 (first Mlp layer) generated-X GEMMs of an FP block are independent and adjacent in
-        the plan: where both run 64-channel tiles at two workgroups per CU they become ONE SLIDE_OP_GEMM_GX_DUAL launch
-        (SLIDE_GX_DUAL=0: two launches).  Op-index tables are re-keyed."""
-        if os.environ.get("SLIDE_GX_DUAL", "1") == "0":
-            return
-        new_ops, remap, i = [], {}, 0
-        self._dual_keep = []
-        flops, nbytes, names = {}, {}, {}
-        while i < len(self.ops):
-            a_, b_ = self.ops[i], self.ops[i + 1] if i + 1 < len(self.ops) else None
-            k = len(new_ops)
-            if (a_ is not None and b_ is not None and a_.kind == OP_GEMM_GX and b_.kind == OP_GEMM_GX and a_.i[6] == 1 and b_.i[6] == 0
-                    and ((a_.f[0] in (1.0, 2.0) and b_.f[0] == 2.0) or (a_.f[0] == 3.0 and b_.f[0] == 3.0))
-                    and a_.i[0] == b_.i[0] and a_.i[4] == b_.i[4] and a_.i[10] == b_.i[10]):
-                pair = (SlideOp * 2)(SlideOp.from_buffer_copy(bytes(a_)), SlideOp.from_buffer_copy(bytes(b_)))
-                self._dual_keep.append(pair)
-                op = make_op(OP_GEMM_GX_DUAL, i=(a_.i[0],), p=(ctypes.addressof(pair),))
-                op.i[10] = a_.i[10]
-                new_ops.append(op)
-                remap[i] = remap[i + 1] = k
-                flops[k] = self.gemm_flops.get(i, 0) + self.gemm_flops.get(i + 1, 0)
-                nbytes[k] = tuple(self.gemm_bytes.get(i, (0, 0))[z] + self.gemm_bytes.get(i + 1, (0, 0))[z] for z in (0, 1))
-                names[k] = ("gemm_gxs_dual_kernel<%d>" if a_.f[0] == 3.0 else "gemm_gx_dual_kernel<%d>") % a_.i[4]
-                i += 2
-                continue
-            new_ops.append(a_)
-            remap[i] = k
-            for src, dst in ((self.gemm_flops, flops), (self.gemm_bytes, nbytes), (self.kernel_names, names)):
-                if i in src:
-                    dst[k] = src[i]
-            i += 1
-        self.ops = new_ops
-        self.gemm_flops, self.gemm_bytes, self.kernel_names = flops, nbytes, names
-        self.xyz_copy_idx = [remap[q] for q in self.xyz_copy_idx]
-        self.eps_copy_idx = remap[self.eps_copy_idx]
-        self._prep_idx = remap[self._prep_idx]
-        self._remap_point_chain(remap)
-        if self.head is not None:
-            self.head["idx"] = [remap[q] for q in self.head["idx"]]
-        self._body_args = {remap[q]: v for q, v in self._body_args.items()}
-        self._tail_of = {k_: remap[v] for k_, v in self._tail_of.items()}
+    # ------------------------------------------------------------------ merge passes: matchers for `rewrite`, in the order _build runs them
+    @staticmethod
+    def _host_op(kind, i, block, keep, lane=0):
+        """an op whose p[0] is a HOST block (ctypes array or int64 record), which `keep` holds alive"""
+        keep.append(block)
+        op = make_op(kind, i=i, p=(block.ctypes.data if isinstance(block, np.ndarray) else ctypes.addressof(block),))
+        op.i[10] = lane
+        return op
 
     def _merge_chains(self):
         """runs of consecutive per-point GEMM launches (16 rows per sample, fp16, plain input) become ONE SLIDE_OP_GEMM_CHAIN
         launch each (csrc/gemm_chain.hip): the FP blocks' second Mlp_plus_t_emb, the output head.  SLIDE_GEMM_CHAIN=0 keeps the
-        launches apart.  Every op-index table of the plan is re-keyed."""
+        launches apart."""
         # SLIDE_GEMM_CHAIN = largest chain in KB of weights (default 0: none).  OPT-IN -- measured in bench.py's arrangement (three
         # feature sub-batches + the position chain): 92 launches per step instead of 108, but 366 shapes/s with every chain
         # merged and 371 with the chains of <= 256 KB of weights against 374 without: a chain's 20-odd workgroups each stream
@@ -1676,55 +1567,105 @@ class DenoiserEngine:
         # store round trips in sequence, where the wide-grid launches of the other chains fill the same CUs meanwhile
         max_kb = int(os.environ.get("SLIDE_GEMM_CHAIN", "0"))
         if self.prec != 1 or not self.use_glds or max_kb <= 0:
-            return
+            return lambda plan, i: None
+
         def eligible(o):
-            return (o is not None and o.kind == OP_GEMM and o.i[4] == 4 and o.i[6] == 1 and o.i[8] == 1 and o.i[9] != 3
+            return (o.kind == OP_GEMM and o.i[4] == 4 and o.i[6] == 1 and o.i[8] == 1 and o.i[9] != 3
                     and not any(o.p[k] for k in (3, 4, 6, 7, 8, 9, 10, 11, 12, 13)) and o.i[2] <= 1024)
-        new_ops, remap, i = [], {}, 0
-        self._chain_keep = []
-        flops, nbytes, names = {}, {}, {}
-        while i < len(self.ops):
-            j = i
-            while (j < len(self.ops) and eligible(self.ops[j]) and self.ops[j].i[0] == self.ops[i].i[0]
-                   and self.ops[j].i[10] == self.ops[i].i[10] and j - i < 6):
+
+        def match(plan, i):
+            o0, j = plan[i].op, i
+            while j < len(plan) and j - i < 6 and eligible(plan[j].op) and plan[j].op.i[0] == o0.i[0] and plan[j].op.i[10] == o0.i[10]:
                 j += 1
-            k = len(new_ops)
-            while j - i >= 2 and sum(o.i[2] * o.i[3] * 64 for o in self.ops[i:j]) > max_kb * 1024:
+            while j - i >= 2 and sum(e.op.i[2] * e.op.i[3] * 64 for e in plan[i:j]) > max_kb * 1024:
                 j -= 1  # (drop layers from the end until the chain's weights fit)
-            if j - i >= 2:
-                tab = (SlideChainLayer * (j - i))()
-                for q, o in enumerate(self.ops[i:j]):
-                    tab[q].X, tab[q].W, tab[q].epi = o.p[0], o.p[1], o.p[2] & ~1  # (strip SLIDE_EPI_PACKED_VECS: this kernel reads the descriptors' pointers)
-                    tab[q].x_ld, tab[q].k_pad, tab[q].n_cob = o.i[1], o.i[2], o.i[3]
-                self._chain_keep.append(tab)
-                op = make_op(OP_GEMM_CHAIN, i=(self.ops[i].i[0], j - i), p=(ctypes.addressof(tab),))
-                op.i[10] = self.ops[i].i[10]
-                new_ops.append(op)
-                for q in range(i, j):
-                    remap[q] = k
-                flops[k] = sum(self.gemm_flops.get(q, 0) for q in range(i, j))
-                nbytes[k] = tuple(sum(self.gemm_bytes.get(q, (0, 0))[z] for q in range(i, j)) for z in (0, 1))
-                names[k] = "gemm_chain_kernel"
-                i = j
-                continue
-            new_ops.append(self.ops[i])
-            remap[i] = k
-            for src, dst in ((self.gemm_flops, flops), (self.gemm_bytes, nbytes), (self.kernel_names, names)):
-                if i in src:
-                    dst[k] = src[i]
-            i += 1
-        self.ops = new_ops
-        self.gemm_flops, self.gemm_bytes, self.kernel_names = flops, nbytes, names
-        self.xyz_copy_idx = [remap[q] for q in self.xyz_copy_idx]
-        self.eps_copy_idx = remap[self.eps_copy_idx]
-        if self.head is not None:
-            self.head["idx"] = [remap[q] for q in self.head["idx"]]
-            if len(set(self.head["idx"])) != 2:
-                self.head = None  # (the head GEMMs went into a chain launch)
-        self._prep_idx = remap[self._prep_idx]
-        self._remap_point_chain(remap)
-        self._body_args = {remap[q]: v for q, v in self._body_args.items()}
-        self._tail_of = {k_: remap[v] for k_, v in self._tail_of.items()}
+            if j - i < 2:
+                return None
+            tab = (SlideChainLayer * (j - i))()
+            for q, e in enumerate(plan[i:j]):
+                o = e.op
+                tab[q].X, tab[q].W, tab[q].epi = o.p[0], o.p[1], o.p[2] & ~1  # (strip SLIDE_EPI_PACKED_VECS: this kernel reads the descriptors' pointers)
+                tab[q].x_ld, tab[q].k_pad, tab[q].n_cob = o.i[1], o.i[2], o.i[3]
+            return j - i, [(self._host_op(OP_GEMM_CHAIN, (o0.i[0], j - i), tab, self._chain_keep, o0.i[10]), "gemm_chain_kernel", plan[i:j])]
+        return match
+
+    def _merge_gx_pairs(self):
+        """the mode-1 (keys -> u) and mode-0 (first Mlp layer) generated-X GEMMs of an FP block are independent and adjacent in
+        the plan: where both run 64-channel tiles at two workgroups per CU they become ONE SLIDE_OP_GEMM_GX_DUAL launch
+        (SLIDE_GX_DUAL=0: two launches)."""
+        if os.environ.get("SLIDE_GX_DUAL", "1") == "0":
+            return lambda plan, i: None
+
+        def match(plan, i):
+            if i + 1 >= len(plan):
+                return None
+            a_, b_ = plan[i].op, plan[i + 1].op
+            if not (a_.kind == OP_GEMM_GX and b_.kind == OP_GEMM_GX and a_.i[6] == 1 and b_.i[6] == 0
+                    and ((a_.f[0] in (1.0, 2.0) and b_.f[0] == 2.0) or (a_.f[0] == 3.0 and b_.f[0] == 3.0))
+                    and a_.i[0] == b_.i[0] and a_.i[4] == b_.i[4] and a_.i[10] == b_.i[10]):
+                return None
+            pair = (SlideOp * 2)(SlideOp.from_buffer_copy(bytes(a_)), SlideOp.from_buffer_copy(bytes(b_)))
+            return 2, [(self._host_op(OP_GEMM_GX_DUAL, (a_.i[0],), pair, self._dual_keep, a_.i[10]),
+                        ("gemm_gxs_dual_kernel<%d>" if a_.f[0] == 3.0 else "gemm_gx_dual_kernel<%d>") % a_.i[4], plan[i:i + 2])]
+        return match
+
+    def _merge_chain_query(self):
+        """SA blocks: [per-point query GEMM P | keys -> u GEMM (needs P) | fused Mlp chain (needs neither)] becomes
+        [chain + query GEMM in ONE launch (SLIDE_OP_SA_CHAIN_P) | keys -> u GEMM]: the query GEMM's launch and gap disappear under
+        the chain (SLIDE_CHAIN_P=0: three launches)."""
+        if os.environ.get("SLIDE_CHAIN_P", "1") == "0":
+            return lambda plan, i: None
+        is_p = lambda o: (o.kind == OP_GEMM and o.i[4] == 4 and o.i[6] == 1 and not (o.i[8] & 6) and o.i[9] != 3 and o.p[3] and o.p[6]
+                          and not any(o.p[k] for k in (8, 9, 10, 11, 12, 13)))
+
+        def match(plan, i):
+            if i + 2 >= len(plan):
+                return None
+            o0, o1, o2 = (e.op for e in plan[i:i + 3])
+            if not (is_p(o0) and o1.kind == OP_GEMM_GX and o1.i[6] == 1 and o2.kind == OP_SA_CHAIN
+                    and o0.i[0] == o2.i[0] * 16 and o0.i[10] == o1.i[10] == o2.i[10]):
+                return None
+            pair = (SlideOp * 2)(SlideOp.from_buffer_copy(bytes(o2)), SlideOp.from_buffer_copy(bytes(o0)))
+            return 3, [(self._host_op(OP_SA_CHAIN_P, (o2.i[0],), pair, self._chain_p_keep, o0.i[10]),
+                        "sa_chain_p_kernel<%d>" % (o2.i[3] // 32), [plan[i], plan[i + 2]]), plan[i + 1]]
+        return match
+
+    def _merge_pp(self):
+        """split plans (round 5): runs of consecutive per-point launches -- 16-row SLIDE_OP_GEMM in the split arithmetic and the float
+        pair-table pass -- become ONE SLIDE_OP_PP_STAGE launch each (csrc/gemm_gxs.hip: one workgroup per sample walks the steps, the
+        dense layers as exact fp32 FMA chains; 30 -> 17 launches per position step).  SLIDE_PP=0 keeps the launches apart."""
+        # OPT-IN (SLIDE_PP=1): measured SLOWER -- one workgroup per sample re-reads every layer's weights per sample and its K loop is a
+        # chain of dependent L2 round trips on four waves: 55 - 131 us per stage launch against 27 - 45 us for the launches it replaces
+        # (position chain alone 365 -> 652 us per step, bench 379 -> 227 shapes/s)
+        if not self.use_gxs or os.environ.get("SLIDE_PP", "0") == "0":
+            return lambda plan, i: None
+        B = self.B
+
+        def step_kind(e):  # 0: dense layer, 1: pair-table pass, None: not a step
+            o = e.op
+            if o.kind == OP_GEMM and e.w16 is not None and o.i[0] == B * 16 and o.i[2] <= 192 and not o.i[10]:
+                return 0
+            if o.kind == OP_PAIR_NORM and o.i[3] == 2 and o.i[4] == 1 and o.i[0] == B and not o.i[10]:
+                return 1
+            return None
+
+        def step(e):
+            o = e.op
+            if step_kind(e) == 1:
+                return [1] + [o.p[k] or 0 for k in range(13)] + [o.i[1], o.i[2]]
+            wt = self.A.put(np.ascontiguousarray(e.w16.T), torch.float32)  # K-major [k_pad][n_cob*32] (only for layers that are merged)
+            return [0, o.p[0], wt.data_ptr(), o.p[2] & ~1, o.p[3] or 0, o.p[4] or 0, o.i[1], o.i[2], o.i[3], o.i[5]] + [0] * 6
+
+        def match(plan, i):
+            kinds, j = [], i
+            while j < len(plan) and len(kinds) < 8 and step_kind(plan[j]) is not None and (step_kind(plan[j]) == 0 or sum(kinds) < 2):
+                kinds.append(step_kind(plan[j]))
+                j += 1
+            if j - i < 2:
+                return None
+            rec = np.array([j - i, B] + [v for e in plan[i:j] for v in step(e)], np.int64)
+            return j - i, [(self._host_op(OP_PP_STAGE, (B, j - i), rec, self._pp_keep), "pp_stage_kernel", plan[i:j])]
+        return match
 
     # ------------------------------------------------------------------ execution
     def run(self, ops_array, n=None):

@@ -14,16 +14,11 @@ class _Mini:
     """just enough of DenoiserEngine to emit one GEMM op"""
 
     def __new__(cls, B, prec, device):
-        import torch
         from slide_amd import engine as E
 
         class M(E.DenoiserEngine):
             def __init__(self):
-                self.B, self.device, self.prec = B, device, E.PREC[prec]
-                self.adt = torch.float16 if self.prec == 1 else torch.float32
-                self.A = E._Arena(device); self.ops = []; self.flops = 0; self.gemm_flops = {}; self.gemm_bytes = {}
-                self.per_sample_t = True; self.two_lanes = False; self._lane = 0
-                self.use_glds = True; self.glds_nst = 0; self.persistent = False
+                self._plan_state(B, device, prec)
         return M()
 
 

@@ -11,11 +11,7 @@ dev = torch.device("cuda:0")
 
 class Mini(E.DenoiserEngine):
     def __init__(self, B, prec):
-        self.B, self.device, self.prec = B, dev, E.PREC[prec]
-        self.adt = torch.float16 if self.prec == 1 else torch.float32
-        self.A = E._Arena(dev); self.ops = []; self.flops = 0; self.gemm_flops = {}
-        self.per_sample_t = True
-        self.two_lanes = False; self._lane = 0; self.gemm_bytes = {}
+        self._plan_state(B, dev, prec)
         self.persistent = os.environ.get('SLIDE_PERSISTENT', '0') != '0'
         self.use_glds = os.environ.get('SLIDE_GLDS', '1') != '0'
         self.glds_nst = int(os.environ.get('SLIDE_GLDS_WIDE', '0'))
