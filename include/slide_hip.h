@@ -131,6 +131,13 @@ SLIDE_API int slide_occupancy_grid(int s, int p, const float *pts, int sp, int r
 SLIDE_API const char *slide_hip_version(void);
 SLIDE_API int slide_hip_device_ok(void); /* 1 if a gfx950 device is visible */
 
+/* Self-test of the GroupNorm epilogues' lane reduction (csrc/lane_reduce.h): ONE 64-lane wave sums nv (4, 8, 16, 32 or 64) fp32
+ * values per lane over each 32-lane half wave, twice.  in (64,nv): lane l's values.  out_old (64,nv): the all-reduce
+ * lane_group_sum<32> of every value, as every lane holds it.  out_new (64, max(nv / 32, 1)): what lane_half_sums leaves in the
+ * lane's registers; register j is the total of value lane_reduce_index<nv>(l) + j (the rule is written out in lane_reduce.h).
+ * Returns -2 for another nv or a NULL pointer. */
+SLIDE_API int slide_lane_reduce_selftest(const float *in, float *out_new, float *out_old, int nv, slide_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

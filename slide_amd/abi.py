@@ -171,6 +171,7 @@ PROTOTYPES = {name: _proto(args) for name, args in {
     "slide_chamfer_pairwise": "iiiipipiipp",
     "slide_occupancy_grid": "iipiippppppp",
     "slide_hip_device_ok": "",
+    "slide_lane_reduce_selftest": "pppip",
     # include/slide_engine.h
     "slide_run_ops": "pip",
     "slide_run_ops2": "pipp",

@@ -22,6 +22,7 @@
 
 #include "gemm_common.h"
 #include "gemm_small.h"
+#include "lane_reduce.h"
 #include "launch.h"
 #include "pair_norm.h"
 
@@ -652,17 +653,6 @@ struct F1Args {
   int nsplit;  // round 6: workgroups per sample (1 | 2): each takes n2 / 256 / nsplit of the stage-2 slabs (stage 1 is computed by all)
 };
 
-// sum over the 32 lanes of a half wave; the total is valid in the half's UPPER 16 lanes (col >= 16).  Pure DPP: four steps
-// inside the 16-lane rows, then row_bcast15 carries row 0 / 2's total into row 1 / 3 (no LDS swizzle round trip).
-__device__ __forceinline__ float half_wave_sum_hi(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));   // xor 1
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));   // xor 2
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));  // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));  // row_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xA, 0xF, false)); // row_bcast15 -> rows 1, 3
-  return v;
-}
-
 // workgroup barrier that orders LDS traffic only: __syncthreads() would also drain the VM counter, i.e. wait for the weight
 // ring's DMA in flight (and for the epilogue's own stores)
 __device__ __forceinline__ void lds_barrier() {
@@ -688,7 +678,7 @@ __device__ __forceinline__ void sa_chain_body(const F1Args &a, const int bid) {
   float *const vec1_l = reinterpret_cast<float *>(smem_raw + (size_t)NST * STAGE_B);  // [3][n1]
   float *const vec2_l = vec1_l + 3 * a.n1;                                            // [3][n2]
   float *const add1_l = vec2_l + 3 * a.n2;                                            // [n1]
-  float *const red = add1_l + a.n1;                                                   // [8 waves][8 cb][2 halves][4][2]
+  float *const red = add1_l + a.n1;                                                   // [8 waves][2 halves][64 values]
   float *const gsh = red + 8 * 8 * 2 * 4 * 2;                                         // [8 cb][2][32]
   T *const add0_l = reinterpret_cast<T *>(gsh + 8 * 2 * 32);                          // [k1] fp16
   unsigned char *const ta_l = reinterpret_cast<unsigned char *>(add0_l + a.k1);
@@ -850,43 +840,89 @@ __device__ __forceinline__ void sa_chain_body(const F1Args &a, const int bid) {
   // GroupNorm of a stage: acc blocks v[NB] (D layout: reg r -> channel (r & 3) + 8 (r >> 2) + 4 half of the block, lane col ->
   // row; bias included since the accumulator init); statistics over the sample's 256 rows x gs channels.  Leaves per-channel
   // scale / shift in gsh.  Written on register PAIRS (packed fp32 VALU ops): these epilogues are VALU-issue bound.
+  // The sums over the wave's 32 rows go through the transposing lane reduction (lane_reduce.h): value q (NB * 2) + 2 cb + {0: sum,
+  // 1: sum of squares} of channel quad q (its pair of quads for groups of 16, folded BEFORE the reduction) of block cb.  The
+  // accumulators and stage 2's B fragments leave some forty registers, so the values are formed two quads at a time and the
+  // levels that pair the quads of a block, then blocks cb and cb + NB / 2, run as soon as their operands exist, each step
+  // behind a scheduling barrier: a dozen values are live at a time, not 64.  The last levels run on the NB values left; every
+  // lane then holds one or two totals of its half wave and all 64 store them at once: red[wave][half][value].
+  auto stats_reduce = [&](auto nb_tag, auto fold_tag, const f32x16 *v) __attribute__((always_inline)) {
+    constexpr int NB = decltype(nb_tag)::value, NQ = decltype(fold_tag)::value ? 2 : 4, NV = NB * NQ * 2;
+    // {sum, sum of squares} of quads qa and qb of a block over the lane's 16 channels x 1 row -> o[0 .. 4)
+    auto quad_pair = [&](const f32x16 &a, int qa, int qb, float *o) __attribute__((always_inline)) {
+      f32x2 t[2], tt[2];
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int q = k ? qb : qa;
+        const f32x2 lo = {a[4 * q], a[4 * q + 1]}, hi = {a[4 * q + 2], a[4 * q + 3]};
+        t[k] = lo + hi;
+        tt[k] = __builtin_elementwise_fma(hi, hi, lo * lo);
+      }
+      o[0] = t[0][0]; o[1] = tt[0][0]; o[2] = t[1][0]; o[3] = tt[1][0];
+      // o += the upper halves: written out, or the compiler packs pairs of these adds and spends three register moves on each
+      // pair.  (A DPP add reads these next, two wait states behind a VALU write: the compiler pads an asm statement's outputs.)
+      asm("v_add_f32 %0, %0, %4\n\tv_add_f32 %1, %1, %5\n\tv_add_f32 %2, %2, %6\n\tv_add_f32 %3, %3, %7"
+          : "+v"(o[0]), "+v"(o[1]), "+v"(o[2]), "+v"(o[3]) : "v"(t[0][1]), "v"(tt[0][1]), "v"(t[1][1]), "v"(tt[1][1]));
+    };
+    // the two values a block leaves after the levels inside it
+    auto block_sums = [&](const f32x16 &a, float *o) __attribute__((always_inline)) {
+      float w[4], x[4];
+      if constexpr (NQ == 2) {
+        quad_pair(a, 0, 1, w);
+        o[0] = w[0] + w[2]; o[1] = w[1] + w[3];
+        __builtin_amdgcn_sched_barrier(0);
+        quad_pair(a, 2, 3, x);
+        o[2] = x[0] + x[2]; o[3] = x[1] + x[3];
+        lane_sum_level<0, 4>(o, lane);
+      } else {
+        quad_pair(a, 0, 2, w);
+        lane_sum_level<0, 4>(w, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        quad_pair(a, 1, 3, x);
+        lane_sum_level<0, 4>(x, lane);
+        o[0] = w[0]; o[1] = w[1]; o[2] = x[0]; o[3] = x[1];
+        lane_sum_level<1, 4>(o, lane);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    float p[NB];
+#pragma unroll
+    for (int k = 0; k < NB / 2; ++k) {
+      float w[4], x[4];
+      block_sums(v[k], w);
+      block_sums(v[k + NB / 2], x);
+      w[2] = x[0]; w[3] = x[1];
+      lane_sum_level<(NQ == 2 ? 1 : 2), 4>(w, lane);
+      p[2 * k] = w[0]; p[2 * k + 1] = w[1];
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (NQ == 2) {
+      lane_sum_level<2, NB>(p, lane);
+      lane_sum_level<3, NB / 2>(p, lane);
+      lane_sum_level<4, (NB == 8 ? 2 : 1)>(p, lane);
+    } else {
+      lane_sum_level<3, NB>(p, lane);
+      lane_sum_level<4, NB / 2>(p, lane);
+    }
+    float *dst = red + (wave * 2 + half) * 64 + lane_reduce_index<NV>(lane);
+    if constexpr (lane_half_regs(NV) == 2) *reinterpret_cast<f32x2 *>(dst) = f32x2{p[0], p[1]};
+    else *dst = p[0];
+  };
   auto group_stats = [&](auto nb_tag, f32x16 *v, const float *vec_l, int cb_base, int n, int gs, float inv_count) __attribute__((always_inline)) {
     constexpr int NB = decltype(nb_tag)::value;
-#pragma unroll
-    for (int cb = 0; cb < NB; ++cb) {
-      float s[4], ss[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x2 lo = {v[cb][4 * q], v[cb][4 * q + 1]}, hi = {v[cb][4 * q + 2], v[cb][4 * q + 3]};
-        const f32x2 t = lo + hi;
-        const f32x2 tt = __builtin_elementwise_fma(hi, hi, lo * lo);
-        s[q] = t[0] + t[1];
-        ss[q] = tt[0] + tt[1];
-      }
-      if (gs == 16) { s[0] += s[1]; ss[0] += ss[1]; s[2] += s[3]; ss[2] += ss[3]; }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (gs == 16 && (q & 1)) continue;
-        s[q] = half_wave_sum_hi(s[q]);
-        ss[q] = half_wave_sum_hi(ss[q]);
-      }
-      if (col == 31) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          *reinterpret_cast<f32x2 *>(red + ((((wave * 8 + cb) * 2 + half) * 4 + q) * 2)) = f32x2{s[q], ss[q]};
-      }
-    }
+    if (gs == 16) stats_reduce(nb_tag, std::true_type(), v);
+    else stats_reduce(nb_tag, std::false_type(), v);
     lds_barrier();
     // one wave per channel block: channel c = lane (lower half), sums its group's partials over the 8 waves
     if (wave < NB && half == 0) {
       const int cb = wave, c = col, q = c >> 3, hh = (c >> 2) & 1;
       f32x2 t = {0.f, 0.f};
+      const int vi = (gs == 16 ? q >> 1 : q) * (NB * 2) + 2 * cb;  // the group's value number (stats_reduce)
 #pragma unroll
       for (int w = 0; w < 8; ++w) {
-        const float *pw = red + (((w * 8 + cb) * 2) * 4) * 2;
-        if (gs == 4) t += *reinterpret_cast<const f32x2 *>(pw + ((hh * 4 + q) * 2));
-        else if (gs == 8) t += *reinterpret_cast<const f32x2 *>(pw + (q * 2)) + *reinterpret_cast<const f32x2 *>(pw + ((4 + q) * 2));
-        else t += *reinterpret_cast<const f32x2 *>(pw + ((q & 2) * 2)) + *reinterpret_cast<const f32x2 *>(pw + ((4 + (q & 2)) * 2));
+        const float *pw = red + w * 128 + vi;
+        if (gs == 4) t += *reinterpret_cast<const f32x2 *>(pw + hh * 64);
+        else t += *reinterpret_cast<const f32x2 *>(pw) + *reinterpret_cast<const f32x2 *>(pw + 64);
       }
       const float mean = t[0] * inv_count;
       const float var = fmaxf(t[1] * inv_count - mean * mean, 0.f);

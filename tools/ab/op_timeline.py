@@ -49,6 +49,8 @@ with torch.cuda.stream(s.stream):
         want = [i for i in range(n) if s.step_ops[i].kind == int(want[0][4:])]
     for idx in (int(v) for v in want):
         op = SlideOp.from_buffer_copy(bytes(s.step_ops[idx]))
+        if op.kind == 35:  # SLIDE_OP_SA_CHAIN_P: p[0] is a HOST pointer to the chain's op and the query GEMM's; the chain alone is timed
+            op = SlideOp.from_buffer_copy(ctypes.string_at(op.p[0], ctypes.sizeof(SlideOp)))
         nwg = 16384
         dbg = torch.zeros(nwg * 16, dtype=torch.int64, device=dev)
         slot = {1: 5, 17: 12, 19: 12, 16: 8, 30: 1, 31: 13}.get(op.kind)
