@@ -112,6 +112,19 @@ SLIDE_API int slide_chamfer_reduce(int b, int n1, int n2, const float *d1, const
  * for more than 2^31 - 1 workgroups (8 * ceil(n / 8) * m); 0 without a launch when m, n, p or q is 0. */
 SLIDE_API int slide_chamfer_pairwise(int m, int n, int p, int q, const float *x, int sx, const float *y, int sy, int symmetric,
                                      float *out, slide_stream_t stream);
+/* All-pairs approximate Earth Mover's Distance of two SETS of fixed-size clouds (the reference's PyTorchEMD approxmatch + matchcost,
+ * forward only), one launch: x (m,p,sx) / y (n,q,sy) f32 row-major, xyz = the first three floats of every point (sx, sy >= 3) ->
+ * out (m,n) f32, out[i][j] = the RAW cost sum_kl d(k,l) match(k,l) with x[i] as xyz1 (p points) and y[j] as xyz2 (q points), d the
+ * squared L2 distance: ten levels exp(-4^7 d) ... exp(-d / 4), 1 of the auction written out in csrc/emd_pairwise.hip; the match
+ * itself is never stored.  Not divided by a point count (the PVD metric divides by p).  NOT symmetric in its arguments:
+ * out(x, y) is not the transpose of out(y, x), so a set against itself is computed in full.  paired != 0: m == n is required and
+ * only the m pairs (i, i) are computed, out (m), out[i] = cost(x[i], y[i]).  One workgroup per ordered pair, no atomics: an entry
+ * depends on its two clouds only -- not on m, n, the pair's position or the form that computed it.  The pair's mass vectors live
+ * in LDS, in double while they fit (p + q <= 9600), in float beyond (p + q <= 19456; p = q = 8192 fits).  Returns -2 for sx or sy < 3, for paired
+ * with m != n, for clouds beyond that limit and for more than 2^31 - 1 workgroups (8 * ceil(n / 8) * m); 0 without a launch when
+ * m, n, p or q is 0. */
+SLIDE_API int slide_emd_pairwise(int m, int n, int p, int q, const float *x, int sx, const float *y, int sy, int paired, float *out,
+                                 slide_stream_t stream);
 
 /* Occupancy counters of S clouds of P points on an R^3 lattice (the JSD metric's grid_counters / grid_bernoulli_rvars), one launch.
  * pts (s,p,sp) f32 row-major, xyz = the first three floats of a point (sp >= 3); axis (r) f32, the strictly ascending cell-centre

@@ -1,5 +1,6 @@
-"""Set-level generation metrics, Chamfer half (reference: pointnet2/models/pvd/metrics/evaluation_metrics.py): MMD-CD, COV-CD and
-1-NNA-CD of a generated set against a reference set, from three all-pairs Chamfer matrices on the GPU.
+"""Set-level generation metrics (reference: pointnet2/models/pvd/metrics/evaluation_metrics.py): MMD, COV and 1-NNA of a generated
+set against a reference set under the Chamfer distance and, on request, the approximate Earth Mover's Distance, from three
+all-pairs matrices per distance on the GPU.
 
 `pairwise_cd`, `lgan_mmd_cov`, `knn` and `compute_all_metrics` keep the reference's names, argument orders, result keys and
 reductions.  A matrix is ONE launch of slide_amd/csrc/chamfer_pairwise.hip (both directions of every pair searched and reduced
@@ -8,7 +9,13 @@ chamfer_and_f1.calc_cd gives for that pair (`cd_t`), wherever the pair sits in t
 
 Scope: CUDA tensors only for `pairwise_cd` / `compute_all_metrics` (no CPU fallback), no autograd (inputs that require grad raise
 NotImplementedError), fixed-size clouds (a set is a dense (M, P, C) tensor).  `lgan_mmd_cov` and `knn` are plain torch and run on
-any device.  The reference's EMD keys are absent: Earth Mover's Distance is not implemented in this project.
+any device.
+
+EMD (`pairwise_emd`, `all_pairs_matrices_emd`, `compute_all_metrics(..., emd=True)`): the second output of the reference's
+`_pairwise_EMD_CD_`, cost / P of its approximate match, on slide_amd/csrc/emd_pairwise.hip -- one workgroup per ORDERED pair (the
+function is not symmetric in its arguments, so a set against itself is computed in full), the match matrix never stored.  It
+costs 30 exponentials per pair of points where Chamfer costs two distance evaluations, so the six EMD keys are opt-in, as JSD is;
+a large matrix runs as several bounded launches.
 
 JSD block (`unit_cube_grid_point_cloud`, `entropy_of_occupancy_grid`, `jensen_shannon_divergence`, `jsd_between_point_cloud_sets`;
 the reference's names, argument lists, defaults and return types): the Jensen-Shannon divergence between the occupancy distributions
@@ -55,6 +62,25 @@ def pairwise_cd(sample_pcs, ref_pcs=None, batch_size=None):
     s = _hip.chamfer_pairwise(x, y)
     P, Q = x.shape[1], (x if y is None else y).shape[1]
     return s[:, :, 0, 0] / P + s[:, :, 1, 0] / Q
+
+
+def pairwise_emd(sample_pcs, ref_pcs=None, batch_size=None):
+    """(N_sample, N_ref) float32 matrix of the approximate Earth Mover's Distance with sample_pcs[i] as xyz1 and ref_pcs[j] as xyz2,
+    divided by the points per sample cloud (the reference's `EMD(sample_batch_exp, ref_batch, transpose=False)` of
+    `_pairwise_EMD_CD_`).  Same inputs and scope as pairwise_cd.  ref_pcs=None scores the set against itself, in full: the
+    distance is not symmetric in its arguments.  batch_size is accepted and ignored (launches are bounded by work, not by memory)."""
+    _check_set(sample_pcs, "sample_pcs")
+    if ref_pcs is not None:
+        _check_set(ref_pcs, "ref_pcs")
+    for t in (sample_pcs, ref_pcs):
+        if t is not None and torch.is_grad_enabled() and t.requires_grad:
+            raise NotImplementedError("metrics_point_cloud.generation_metrics is forward only (no backward kernels): call it under "
+                                      "torch.no_grad() or on tensors that do not require grad")
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("metrics_point_cloud.generation_metrics runs on the GPU only: got a %s tensor" % t.device)
+    x = sample_pcs.detach().float()
+    y = None if ref_pcs is None else ref_pcs.detach().float()
+    return _hip.emd_pairwise(x, y) / x.shape[1]
 
 
 def lgan_mmd_cov(all_dist):
@@ -113,18 +139,32 @@ def all_pairs_matrices(sample_pcs, ref_pcs):
     return pairwise_cd(ref_pcs, sample_pcs), pairwise_cd(ref_pcs), pairwise_cd(sample_pcs)
 
 
-def compute_all_metrics(sample_pcs, ref_pcs, batch_size=None):
+def all_pairs_matrices_emd(sample_pcs, ref_pcs):
+    """the three EMD matrices of compute_all_metrics(emd=True): (M_rs (N_ref, N_sample), M_rr, M_ss), float32 on the device, every
+    one computed in full"""
+    return pairwise_emd(ref_pcs, sample_pcs), pairwise_emd(ref_pcs), pairwise_emd(sample_pcs)
+
+
+def compute_all_metrics(sample_pcs, ref_pcs, batch_size=None, emd=False):
     """MMD-CD, COV-CD and 1-NNA-CD of sample_pcs (N_s, P, C >= 3) against ref_pcs (N_r, Q, C >= 3), CUDA tensors -> dict of 0-dim
     device tensors with the reference's CD keys: lgan_mmd-CD, lgan_cov-CD, lgan_mmd_smp-CD, 1-NN-CD-acc_t, 1-NN-CD-acc_f,
     1-NN-CD-acc.  Three launches (references x samples, references x references and samples x samples in the symmetric form);
     the (N_r + N_s)^2 matrix of the 1-NN test stays on the device.  batch_size is accepted and ignored.
 
-    The reference's EMD keys (lgan_*-EMD, 1-NN-EMD-*) are absent: this project has no Earth Mover's Distance."""
+    emd=True adds the reference's six EMD keys (lgan_mmd-EMD, lgan_cov-EMD, lgan_mmd_smp-EMD, 1-NN-EMD-acc_t, 1-NN-EMD-acc_f,
+    1-NN-EMD-acc) from three more matrices (all_pairs_matrices_emd) through the same lgan_mmd_cov and knn; the CD values do not
+    change.  Off by default: the EMD matrices cost far more than the Chamfer ones."""
     with torch.no_grad():
         M_rs_cd, M_rr_cd, M_ss_cd = all_pairs_matrices(sample_pcs, ref_pcs)
         results = {"%s-CD" % k: v for k, v in lgan_mmd_cov(M_rs_cd.t()).items()}
+        if emd:
+            M_rs_emd, M_rr_emd, M_ss_emd = all_pairs_matrices_emd(sample_pcs, ref_pcs)
+            results.update({"%s-EMD" % k: v for k, v in lgan_mmd_cov(M_rs_emd.t()).items()})
         one_nn_cd_res = knn(M_rr_cd, M_rs_cd, M_ss_cd, 1, sqrt=False)
         results.update({"1-NN-CD-%s" % k: v for k, v in one_nn_cd_res.items() if 'acc' in k})
+        if emd:
+            one_nn_emd_res = knn(M_rr_emd, M_rs_emd, M_ss_emd, 1, sqrt=False)
+            results.update({"1-NN-EMD-%s" % k: v for k, v in one_nn_emd_res.items() if 'acc' in k})
     return results
 
 

@@ -346,6 +346,43 @@ def chamfer_pairwise(x, y=None):
     return out
 
 
+# point-pair evaluations (one exponential each: rows * N * P * Q * 3 sweeps * 10 levels) one launch of emd_pairwise may cover; a
+# larger matrix is split into row blocks.  The kernel was measured at 3.9e12 evaluations/s on an MI355X (profiles/pairwise_emd.md),
+# so a launch stays under a second: other work shares the device.
+EMD_EVALS_PER_PAIR_OF_POINTS = 30
+EMD_EVALS_PER_LAUNCH = 3.5e12
+
+
+def emd_pairwise(x, y=None, paired=False, max_evals=None):
+    """all-pairs approximate Earth Mover's Distance of two sets of fixed-size clouds (include/slide_hip.h slide_emd_pairwise): x
+    (M,P,C>=3), y (N,Q,C>=3) f32 CUDA tensors (xyz = channels 0:3, read in place) -> (M,N) f32, [i][j] = the raw cost with x[i] as
+    xyz1 and y[j] as xyz2 (not divided by a point count; not symmetric in its arguments).  y=None: the set against itself,
+    computed in full.  paired=True: M == N and only the pairs (i, i) -> (M,).  A large matrix is split into row-block launches of
+    at most max_evals (default EMD_EVALS_PER_LAUNCH) exponentials each, at least one row; every entry is bit-equal to what one
+    launch gives, and to the paired form's."""
+    x, sx = _pts3(x, "x")
+    if y is None:
+        y, sy = x, sx
+    else:
+        y, sy = _pts3(y, "y")
+        if y.device != x.device:
+            raise RuntimeError("x and y must be on the same device")
+    M, P, N, Q = x.size(0), x.size(1), y.size(0), y.size(1)
+    if paired and M != N:
+        raise RuntimeError("emd_pairwise: the paired form needs as many clouds in y as in x")
+    if M and N and not (P and Q):
+        raise RuntimeError("emd_pairwise: clouds must hold at least one point")
+    out = torch.empty((M,) if paired else (M, N), device=x.device, dtype=torch.float32)
+    per_row = float(EMD_EVALS_PER_PAIR_OF_POINTS) * (1 if paired else max(N, 1)) * max(P, 1) * max(Q, 1)
+    rows = int(max(1.0, min(float(max(M, 1)), (EMD_EVALS_PER_LAUNCH if max_evals is None else max_evals) // per_row)))
+    for r0 in range(0, max(M, 1), rows):
+        r1 = min(M, r0 + rows)
+        yb = y[r0:r1] if paired else y
+        check(lib().slide_emd_pairwise(r1 - r0, yb.size(0), P, Q, ptr(x[r0:r1]), sx, ptr(yb), sy, int(bool(paired)), ptr(out[r0:r1]),
+                                       stream_of()), "emd_pairwise")
+    return out
+
+
 def occupancy_grid(points, axis, mask, return_cells=False):
     """occupancy counters of a set of clouds on an R^3 lattice in one launch (include/slide_hip.h slide_occupancy_grid): points
     (S,P,C>=3) f32 CUDA tensor (xyz = channels 0:3, read in place), axis (R,) f32 cell-centre coordinates of one axis (strictly

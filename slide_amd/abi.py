@@ -169,6 +169,7 @@ PROTOTYPES = {name: _proto(args) for name, args in {
     "slide_chamfer_nn": "iiipipippppppp",
     "slide_chamfer_reduce": "iiippppppfiipipipp",
     "slide_chamfer_pairwise": "iiiipipiipp",
+    "slide_emd_pairwise": "iiiipipiipp",
     "slide_occupancy_grid": "iipiippppppp",
     "slide_hip_device_ok": "",
     "slide_lane_reduce_selftest": "pppip",
