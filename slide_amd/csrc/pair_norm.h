@@ -27,10 +27,11 @@ __device__ __forceinline__ void pair_norm2_body(int ld, const float *__restrict_
   __shared__ float grp[32][2];
   const int tid = threadIdx.x;
   if (tid < 48) sx[tid] = xyz[(size_t)b * 48 + tid];
-  if (FP && tid < 128) {
-    const int slot = (b * 16 + (tid >> 3)) * 16 + (tid & 7);
-    sq[tid] = nbr[slot]; sd[tid] = d2t[slot]; sw[tid] = wt[slot];
-  }
+  if (FP)
+    for (int t = tid; t < 128; t += nthr) {  // (ld <= 64 launches a single wave: fewer threads than the sample's 16 x 8 slots)
+      const int slot = (b * 16 + (t >> 3)) * 16 + (t & 7);
+      sq[t] = nbr[slot]; sd[t] = d2t[slot]; sw[t] = wt[slot];
+    }
   SlideGnFin f = {};
   if (finp) {
     f = *finp;

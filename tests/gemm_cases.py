@@ -234,9 +234,11 @@ def _split(a):
     return hi, r16((a - hi) * 2048.0)
 
 
-def forward(c, d, mutant=None, fin=None):
+def forward(c, d, mutant=None, fin=None, xb=None):
     """float64 reference of the case (or of one of its mutants).  fin: the scale / shift the launch published (statistics
-    finalisation cases: the GEMM's operands are their fp16 copies).  Returns dict(y = output [rows][N], A, b = bound,
+    finalisation cases: the GEMM's operands are their fp16 copies).  xb: elementwise uncertainty [rows][K] of an X that its
+    producer hands over in registers (tests/pair_cases.py): X is then taken as given -- its rounding is part of xb -- and
+    the contraction's bound gains xb . |W|^T.  Returns dict(y = output [rows][N], A, b = bound,
     stats = (sum, sq) [B][N] or None, stats_b)."""
     prec, B, K, N, npxl = c["prec"], c["B"], c["K"], c["N"], c["npxl"]
     npx = 1 << npxl
@@ -246,7 +248,7 @@ def forward(c, d, mutant=None, fin=None):
     X = d["X"].astype(np.float64)
     W = d["W"].astype(np.float64)
     if h:
-        X, W = r16(X), r16(W)
+        X, W = (r16(X) if xb is None else X), r16(W)
     Xabs = np.abs(X)
     if c["aff"]:
         if c["gn_fin"]:
@@ -282,6 +284,8 @@ def forward(c, d, mutant=None, fin=None):
         y = y + pre[prow]
         A = A + np.abs(pre[prow])
     b = C_ACC * A
+    if xb is not None:
+        b = b + xb @ np.abs(W).T
     if c["pre_relu"]:
         y = np.maximum(y, 0)
     stats = stats_b = None
