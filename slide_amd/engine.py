@@ -11,6 +11,7 @@ torch is used for device memory and streams only; all arithmetic runs in libslid
 """
 import ctypes
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -19,6 +20,34 @@ from ._lib import SlideHipError, check, lib
 # the C side of include/slide_engine.h -- every OP_* / EPI_* / F_* constant, PREC, the struct mirrors, make_op and ru -- is declared
 # in abi.py; all of it stays importable from this module
 from .abi import *  # noqa: F401,F403
+
+
+class GnLayout(NamedTuple):
+    """physical channel layout of a GroupNorm'ed (or plain) segment, see gn_layout"""
+    index: np.ndarray  # physical channel of every logical channel
+    width: int         # physical channels
+    n_norm: int        # physical channels that are normalised (the leading ones)
+    gs: int            # group size, physical: a power of two
+    gs_logical: int    # group size, logical: what the statistics are divided by
+
+    @classmethod
+    def plain(cls, C):
+        """C channels where they are, none normalised"""
+        return cls(np.arange(C), C, 0, 1, 1)
+
+    @property
+    def unpermuted(self):
+        """every channel where it logically is (no padded groups)"""
+        return np.array_equal(self.index, np.arange(len(self.index)))
+
+    @property
+    def identity(self):
+        """unpermuted and every channel normalised"""
+        return self.unpermuted and self.width == len(self.index) and self.n_norm == len(self.index)
+
+    def raw(self):
+        """the same columns, no normalisation"""
+        return GnLayout(self.index, self.width, 0, 1, 1)
 
 
 def gn_layout(C):
@@ -36,7 +65,121 @@ def gn_layout(C):
     idx = np.empty(C, np.int64)
     for c in range(C):
         idx[c] = (c // gs) * gs_p + c % gs if c < n_norm else G * gs_p + (c - n_norm)
-    return idx, int(G * gs_p + (C - n_norm)), int(G * gs_p), int(gs_p), int(gs)
+    return GnLayout(idx, int(G * gs_p + (C - n_norm)), int(G * gs_p), int(gs_p), int(gs))
+
+
+# the tuples a segment dict (DenoiserEngine._gemm) carries, by name.  Callers may pass plain tuples: _segment coerces them once
+class AddVec(NamedTuple):
+    """per-sample vector added after the activation: row (sample, or idx[0] of a per-timestep table) of `vec`, from column `off`"""
+    vec: torch.Tensor
+    off: int
+    bs: int                      # per-sample stride
+    idx: torch.Tensor = None     # device-side row index (None: the sample's own row)
+    idx_stride: int = 0          # stride of the rows `idx` selects
+
+
+class PreAdd(NamedTuple):
+    """pre-activation add of a per-point table: row (output row >> shift), or shift < 0: row of the NEIGHBOUR point (K = 2^-shift)"""
+    table: torch.Tensor
+    shift: int
+    coff: int = 0
+
+
+class ResPair(NamedTuple):
+    """PAIR residual: residual(p, j) = ta[q] + tb[p] (+ d2 vd + w vw): ta, tb tables, first column, vv = vd | vw fp32 [2][Opad] for
+    the 8-neighbour samples or None"""
+    ta: torch.Tensor
+    tb: torch.Tensor
+    coff: int
+    vv: torch.Tensor
+
+
+class Stats(NamedTuple):
+    """per-sample channel sums / sums of squares of a STATS segment, from column `coff`, scaled by `scale`"""
+    sum: torch.Tensor
+    sq: torch.Tensor
+    coff: int
+    scale: float
+
+
+class Gather(NamedTuple):
+    """the leading `chunks` 32-column chunks of X are gathered from the neighbours' rows of `table`"""
+    table: torch.Tensor
+    nbr: torch.Tensor
+    K: int
+    chunks: int
+
+
+class InAffine(NamedTuple):
+    """per-sample input affine x * scale + shift, from column `off`, per-sample stride `bs`"""
+    scale: torch.Tensor
+    shift: torch.Tensor
+    off: int
+    bs: int
+
+
+def _rec(T, v):
+    """a plain tuple (or None) as the record T"""
+    return None if v is None else T(*v)
+
+
+_SEG_RECORDS = dict(layout=GnLayout, addvec=AddVec, pre_add=PreAdd, res_pair=ResPair, stats=Stats)
+
+
+def _segment(sg):
+    """a copy of a segment dict with its tuples as records and its layout filled in (no layout: the channels where they are)"""
+    sg = dict(sg)
+    for k, T in _SEG_RECORDS.items():
+        sg[k] = _rec(T, sg.get(k))
+    if sg["layout"] is None:
+        sg["layout"] = GnLayout.plain(sg["w"].shape[0])
+    return sg
+
+
+def seg_offsets(segs):
+    """(first physical column of every segment, total width) of segments stored side by side, each padded to 32 channels"""
+    offs, off = [], 0
+    for sg in segs:
+        offs.append(off)
+        lay = _rec(GnLayout, sg.get("layout"))
+        off += ru(sg["w"].shape[0] if lay is None else lay.width)
+    return offs, off
+
+
+def chunk_major(w):
+    """weights [n][k] -> [k / 32][n][32]"""
+    return np.ascontiguousarray(w.reshape(w.shape[0], -1, 32).transpose(1, 0, 2))
+
+
+def epi_vectors(lay, n, bias=None, gn=None):
+    """[bias | gamma | beta] as float rows [3][n], in the physical channel order of `lay`"""
+    v = np.zeros((3, n), np.float32)
+    if bias is not None:
+        v[0, lay.index] = bias
+    if gn is not None:
+        gam, bet = gn
+        v[1, lay.index[:gam.shape[0]]] = gam
+        v[2, lay.index[:bet.shape[0]]] = bet
+    return v
+
+
+class _Layer(NamedTuple):
+    """a layer as _gemm packs it, before an emitter makes a launch of it"""
+    segs: list           # the segments (_segment)
+    widths: list         # padded physical width of every segment
+    W: np.ndarray        # float weights [n_cob * 32][ld], row-major
+    Wd: torch.Tensor     # the same on the device, in the layer's storage type and order
+    w_cm: bool           # Wd is chunk-major
+    epi: torch.Tensor    # descriptor array (+ packed vectors)
+    epi_ptr: int         # its address as the ops carry it (bit 0: SLIDE_EPI_PACKED_VECS)
+    n_cob: int
+    ld: int
+    rows: int
+    flops: int
+
+    def written(self):
+        """bytes the layer's outputs take"""
+        return sum(self.rows * n * sg["out"].element_size() for sg, n in zip(self.segs, self.widths) if sg["out"] is not None)
 
 
 class _Arena:
@@ -226,7 +369,7 @@ class DenoiserEngine:
         return bool(self.use_cm and self.use_gx and self.prec == 1 and self.use_glds and env("SLIDE_FM", "1") != "0"
                     and env("SLIDE_ATTN_TAIL", "1") != "0" and env("SLIDE_TAIL_RX", "1") != "0" and env("SLIDE_TAIL8", "0") == "0"
                     and env("SLIDE_TAIL_OCC3", "0") == "0" and "SLIDE_TAIL_WIDE" not in os.environ and env("SLIDE_BODY", "0") == "0"
-                    and npx_log2 in (7, 8) and (ru(n_mo) // 32) % 4 == 0 and np.array_equal(gn_layout(cout)[0], np.arange(cout)))
+                    and npx_log2 in (7, 8) and (ru(n_mo) // 32) % 4 == 0 and gn_layout(cout).unpermuted)
 
     def _ldp(self, t):
         """leading dimension as the kernels see it"""
@@ -271,66 +414,24 @@ class DenoiserEngine:
         self._cvec.append((prefix, width))
         return off
 
-    def _gemm(self, X, npx_log2, segs, in_cols=None, in_affine=None, gather=None, gn_fin=None,
-              pre_gather=None, gx=None, pair_tabs=None, pair_fused=None, defer=None, chain=None):
-        """X: input buffer [rows][ld].  segs: list of dicts describing consecutive output segments:
-             w (O,I) bias (O) | out (tensor) out_coff | mode flags | gn=(gamma,beta) for NORM | layout (gn_layout) |
-             addvec=(tensor, off, bs) | residual tensor | bcast | stats=(sum,sq tensors, coff, scale)
-           in_cols: physical column index of every logical input channel (None = identity)."""
-        if defer is not None:  # a layer CHAINED onto a split generated-X GEMM (csrc/gemm_gxs.hip): packed, not launched
-            rows, ld, x_ld = defer["rows"], defer["k_pad"], defer["k_pad"]
-            assert X is None and self.use_gxs and gather is None and gn_fin is None and gx is None and in_affine is None
-        elif gx is not None:  # generated-X GEMM of the pair decomposition (SLIDE_OP_GEMM_GX): X is never stored
-            rows, ld, x_ld = gx["rows"], gx["k_pad"], 32
-            assert X is None and gather is None and gn_fin is None and npx_log2 in (7, 8) and (self.use_cm or self.use_gxs)
-        else:
-            rows, ld = X.shape
-            x_ld = self._ldp(X)
-            assert not self._is_cm(X) or (npx_log2 >= 7 and gather is None)
-            assert not self._is_fm(X), "fragment-major buffers are read by the register-X attention tail only"
-        if gather is not None:  # (feature table, neighbour table, K, chunks read from the table): X holds the remaining columns
-            ld = gather[3] * 32 + ld
-        npx = 1 << npx_log2
-        wrows, tables = [], []
-        vec_list = []
-        for sg in segs:
-            w = sg["w"]
-            O, I = w.shape
-            lay = sg.get("layout")
-            if lay is None:
-                oidx, Op, n_norm_p, gs_p, gs_l = np.arange(O), O, 0, 1, 1
-            else:
-                oidx, Op, n_norm_p, gs_p, gs_l = lay
-            Opad = ru(Op)
-            wp = np.zeros((Opad, ld), np.float32)
-            cols = np.arange(I) if in_cols is None else in_cols
-            wp[np.ix_(oidx, cols)] = w
-            wrows.append(wp)
-            vec = np.zeros((3, Opad), np.float32)
-            if sg.get("bias") is not None:
-                vec[0, oidx] = sg["bias"]
-            if sg.get("gn") is not None:
-                gam, bet = sg["gn"]
-                nn = gam.shape[0]
-                vec[1, oidx[:nn]] = gam
-                vec[2, oidx[:nn]] = bet
-            vec_list.append((vec, sg, Opad, n_norm_p, gs_p, gs_l))
-        W = np.concatenate(wrows, axis=0)
-        n_cob = W.shape[0] // 32
-        # chunk-major weights [k / 32][n][32] for the ring kernels of the 128- / 256-row samples (the 16-row launches run the
-        # split-K small-launch kernel, which reads row-major weights)
-        w_cm = bool(self.use_cm and npx_log2 >= 7) or (gx is not None and self.prec == 1)
-        Wst = np.ascontiguousarray(W.reshape(W.shape[0], ld // 32, 32).transpose(1, 0, 2)) if w_cm else W
-        Wd = self.A.put(Wst, torch.float16 if self.prec == 1 else torch.float32)
-        epis = (SlideEpi * n_cob)()
+    def _pack_epi(self, segs, npx, rows=None, npx_log2=None, chain=None, pair_tabs=None, pre_gather=None, bare=False):
+        """the SlideEpi descriptors of a layer's segments (_segment), one per 32 physical channels, and their packed vectors, in one
+        walk -> (descriptor bytes, [bias | gamma | beta] of every block [n_cob][3][32]).  bare: no weights, no outputs, no bias --
+        only what SLIDE_OP_PAIR_NORM reads: mode, flags, GroupNorm layout / parameters, statistics pointers"""
+        n_cob = sum(ru(sg["layout"].width) for sg in segs) // 32
+        epis, pv = (SlideEpi * n_cob)(), np.zeros((n_cob, 3, 32), np.float32)
         blk = 0
-        for vec, sg, Opad, n_norm_p, gs_p, gs_l in vec_list:
-            vd = self.A.put(vec)
+        for sg in segs:
+            lay = sg["layout"]
+            Opad = ru(lay.width)
+            vec = epi_vectors(lay, Opad, None if bare else sg.get("bias"), sg.get("gn"))
+            vd = self.A.put(vec[1:] if bare else vec)
+            gamma = vd.data_ptr() + 4 * (0 if bare else Opad)
             out = sg["out"]
             coff = sg.get("out_coff", 0)
             flags = sg.get("flags", 0)
             if out is None:  # (the layer's output stays in the chaining kernel's registers)
-                assert chain is not None and len(segs) == 1
+                assert bare or (chain is not None and len(segs) == 1)
             else:
                 assert out.shape[1] >= coff + Opad and coff % (32 if self._is_cm(out) else 8) == 0, (out.shape, coff, Opad)
                 assert out.shape[0] == rows, (out.shape, rows)
@@ -343,97 +444,145 @@ class DenoiserEngine:
                     flags |= F_OUT_FM
             for j in range(Opad // 32):
                 e = epis[blk]
+                pv[blk] = vec[:, 32 * j:32 * j + 32]
                 e.mode = sg.get("mode", EPI_RAW)
                 e.flags = flags
-                e.gs = gs_p
-                e.n_norm = int(min(32, max(0, n_norm_p - 32 * j)))
-                e.inv_count = 1.0 / (gs_l * sg.get("npx", npx))  # (npx: a pair segment's GroupNorm runs over the K-expanded rows)
+                e.gs = lay.gs
+                e.n_norm = int(min(32, max(0, lay.n_norm - 32 * j)))
+                e.inv_count = 1.0 / (lay.gs_logical * sg.get("npx", npx))  # (npx: a pair segment's GroupNorm runs over the K-expanded rows)
                 e.out_ld = 0 if out is None else self._ldp(out)
-                e.bias = vd.data_ptr() + 4 * (32 * j)
-                e.gamma = vd.data_ptr() + 4 * (Opad + 32 * j)
-                e.beta = vd.data_ptr() + 4 * (2 * Opad + 32 * j)
+                e.bias = None if bare else vd.data_ptr() + 4 * (32 * j)
+                e.gamma = gamma + 4 * (32 * j)
+                e.beta = gamma + 4 * (Opad + 32 * j)
                 e.out = None if out is None else self._colptr(out, coff + 32 * j)
-                if sg.get("addvec") is not None:
-                    t, off, bs, idx, idx_stride = sg["addvec"]
-                    assert off % 4 == 0 and bs % 4 == 0 and idx_stride % 4 == 0
-                    e.addvec = t.data_ptr() + 4 * (off + 32 * j)
-                    e.addvec_bs = bs
-                    if idx is not None:
-                        e.addvec_idx = idx.data_ptr()
-                        e.addvec_idx_stride = idx_stride
-                if sg.get("res_pair") is not None:
-                    # PAIR residual: residual(p, j) = ta[q] + tb[p] (+ d2 vd + w vw): (ta, tb fp16 tables, column offset,
-                    # vd | vw fp32 [2][Opad] for the 8-neighbour samples or None)
-                    rta, rtb, rcoff, rvv = sg["res_pair"]
-                    assert rta.dtype == (torch.float16 if self.prec == 1 else torch.float32) and rta.shape == rtb.shape
-                    assert rta.shape[0] == self.B * 16 and (rcoff + 32 * j) % 8 == 0 and rta.shape[1] >= rcoff + Opad
-                    e.residual = rta.data_ptr() + rta.element_size() * (rcoff + 32 * j)
-                    e.res_b = rtb.data_ptr() + rta.element_size() * (rcoff + 32 * j)
-                    e.res_ld = rta.shape[1]
-                    if rvv is None:
+                add = sg["addvec"]
+                if add is not None:
+                    assert add.off % 4 == 0 and add.bs % 4 == 0 and add.idx_stride % 4 == 0
+                    e.addvec = add.vec.data_ptr() + 4 * (add.off + 32 * j)
+                    e.addvec_bs = add.bs
+                    if add.idx is not None:
+                        e.addvec_idx = add.idx.data_ptr()
+                        e.addvec_idx_stride = add.idx_stride
+                rp = sg["res_pair"]
+                if rp is not None:
+                    assert rp.ta.dtype == (torch.float16 if self.prec == 1 else torch.float32) and rp.ta.shape == rp.tb.shape
+                    assert rp.ta.shape[0] == self.B * 16 and (rp.coff + 32 * j) % 8 == 0 and rp.ta.shape[1] >= rp.coff + Opad
+                    e.residual = rp.ta.data_ptr() + rp.ta.element_size() * (rp.coff + 32 * j)
+                    e.res_b = rp.tb.data_ptr() + rp.ta.element_size() * (rp.coff + 32 * j)
+                    e.res_ld = rp.ta.shape[1]
+                    if rp.vv is None:
                         assert npx_log2 == 8
                         e.flags |= F_RES_PAIR
                     else:
                         assert npx_log2 == 7 and pair_tabs is not None
                         e.flags |= F_RES_PAIR_NBR
-                        e.res_vd = rvv.data_ptr() + 4 * (32 * j)
-                        e.res_vw = rvv.data_ptr() + 4 * (Opad + 32 * j)
+                        e.res_vd = rp.vv.data_ptr() + 4 * (32 * j)
+                        e.res_vw = rp.vv.data_ptr() + 4 * (Opad + 32 * j)
                 if sg.get("residual") is not None:
                     r = sg["residual"]
                     assert r.shape[0] == rows and r.shape[1] >= Opad and r.dtype == self.adt
                     e.residual = self._colptr(r, 32 * j)
                     e.res_ld = self._ldp(r)
-                if sg.get("pre_add") is not None:
-                    pa, shift = sg["pre_add"][:2]
-                    pcoff = sg["pre_add"][2] if len(sg["pre_add"]) > 2 else 0
+                pa = sg["pre_add"]
+                if pa is not None:
                     # shift < 0: row of the NEIGHBOUR point (K = 2^-shift), through the table passed as pre_gather
-                    assert pa.shape[0] == (rows >> shift if shift >= 0 else rows >> npx_log2 << 4), (pa.shape, rows, shift)
-                    assert (shift >= 0 or pre_gather is not None) and pa.shape[1] >= pcoff + Opad and pa.dtype == self.adt
-                    assert not self._is_cm(pa)
-                    e.pre_add = pa.data_ptr() + pa.element_size() * (pcoff + 32 * j)
-                    e.pre_add_ld = pa.shape[1]
-                    e.pre_add_shift = shift
-                if sg.get("stats") is not None:
-                    ssum, ssq, scoff, scale = sg["stats"]
-                    e.stats_sum = ssum.data_ptr() + 4 * (scoff + 32 * j)
-                    e.stats_sq = ssq.data_ptr() + 4 * (scoff + 32 * j)
-                    e.stats_bs = ssum.shape[1]
-                    e.stats_scale = scale
+                    assert pa.table.shape[0] == self._pre_add_rows(pa, rows, npx_log2), (pa.table.shape, rows, pa.shift)
+                    assert (pa.shift >= 0 or pre_gather is not None) and pa.table.shape[1] >= pa.coff + Opad and pa.table.dtype == self.adt
+                    assert not self._is_cm(pa.table)
+                    e.pre_add = pa.table.data_ptr() + pa.table.element_size() * (pa.coff + 32 * j)
+                    e.pre_add_ld = pa.table.shape[1]
+                    e.pre_add_shift = pa.shift
+                st = sg["stats"]
+                if st is not None:
+                    e.stats_sum = st.sum.data_ptr() + 4 * (st.coff + 32 * j)
+                    e.stats_sq = st.sq.data_ptr() + 4 * (st.coff + 32 * j)
+                    e.stats_bs = st.sum.shape[1]
+                    e.stats_scale = st.scale
                 blk += 1
+        assert blk == n_cob
+        return np.frombuffer(bytes(epis), dtype=np.uint8), pv
+
+    @staticmethod
+    def _pre_add_rows(pa, rows, npx_log2):
+        """rows of the per-point table a pre_add reads (unique rows)"""
+        return rows >> pa.shift if pa.shift >= 0 else rows >> npx_log2 << 4
+
+    def _epi_only(self, segs, npx):
+        """device array of SlideEpi descriptors (one per 32 physical channels) carrying only what SLIDE_OP_PAIR_NORM reads:
+        mode, flags, GroupNorm layout / parameters, statistics pointers"""
+        return self.A.put(self._pack_epi([_segment(sg) for sg in segs], npx, bare=True)[0].copy())
+
+    def _pack_layer(self, segs, npx_log2, rows, ld, in_cols, w_cm, **epi_kw):
+        """weights and epilogue of a layer on the device (_Layer): the segments' weights stacked in their physical channel order,
+        input channels at `in_cols`; descriptors and packed vectors in one block"""
+        segs = [_segment(sg) for sg in segs]
+        widths = [ru(sg["layout"].width) for sg in segs]
+        wrows = []
+        for sg, Opad in zip(segs, widths):
+            w = sg["w"]
+            wp = np.zeros((Opad, ld), np.float32)
+            wp[np.ix_(sg["layout"].index, np.arange(w.shape[1]) if in_cols is None else in_cols)] = w
+            wrows.append(wp)
+        W = np.concatenate(wrows, axis=0)
+        Wd = self.A.put(chunk_major(W) if w_cm else W, torch.float16 if self.prec == 1 else torch.float32)
         # PACKED VECTORS (SLIDE_EPI_PACKED_VECS, include/slide_engine.h): the blocks' [bias | gamma | beta] values behind the descriptor
         # array, bit 0 of the pointer the ops carry says so -- the kernels stage both by LDS-DMA instead of chasing the three pointers
         # of every block in every workgroup's prologue (SLIDE_PACKED_VECS=0: plain pointer, A/B)
-        pv = np.zeros((n_cob, 3, 32), np.float32)
-        blk = 0
-        for vec, sg, Opad, _n, _g, _l in vec_list:
-            v3 = np.asarray(vec, np.float32).reshape(3, Opad)
-            for j in range(Opad // 32):
-                pv[blk] = v3[:, 32 * j:32 * j + 32]
-                blk += 1
-        assert blk == n_cob
-        ed = self.A.put(np.concatenate([np.frombuffer(bytes(epis), dtype=np.uint8), pv.reshape(-1).view(np.uint8)]))
+        epis, pv = self._pack_epi(segs, 1 << npx_log2, rows, npx_log2, **epi_kw)
+        ed = self.A.put(np.concatenate([epis, pv.reshape(-1).view(np.uint8)]))
         edp = ed.data_ptr() | (1 if os.environ.get("SLIDE_PACKED_VECS", "1") != "0" else 0)
-        sc = sh = None
-        in_bs = aff_off = 0
-        if in_affine is not None:
-            sc, sh, aff_off, in_bs = in_affine
+        return _Layer(segs, widths, W, Wd, w_cm, ed, edp, W.shape[0] // 32, ld, rows, 2 * rows * sum(int(sg["w"].size) for sg in segs))
+
+    def _gemm(self, X, npx_log2, segs, in_cols=None, in_affine=None, gather=None, gn_fin=None,
+              pre_gather=None, gx=None, pair_tabs=None, pair_fused=None, defer=None, chain=None):
+        """X: input buffer [rows][ld].  segs: list of dicts describing consecutive output segments:
+             w (O,I) bias (O) | out (tensor) out_coff | mode flags | gn=(gamma,beta) for NORM | layout (gn_layout) |
+             addvec (AddVec) | residual tensor | res_pair (ResPair) | pre_add (PreAdd) | stats (Stats)
+           in_cols: physical column index of every logical input channel (None = identity).
+           in_affine (InAffine), gather (Gather): X holds the columns that are not gathered."""
+        in_affine, gather = _rec(InAffine, in_affine), _rec(Gather, gather)
+        if defer is not None:  # a layer CHAINED onto a split generated-X GEMM (csrc/gemm_gxs.hip): packed, not launched
+            rows, ld = defer["rows"], defer["k_pad"]
+            assert X is None and self.use_gxs and gather is None and gn_fin is None and gx is None and in_affine is None
+        elif gx is not None:  # generated-X GEMM of the pair decomposition (SLIDE_OP_GEMM_GX): X is never stored
+            rows, ld = gx["rows"], gx["k_pad"]
+            assert X is None and gather is None and gn_fin is None and npx_log2 in (7, 8) and (self.use_cm or self.use_gxs)
+        else:
+            rows, ld = X.shape
+            assert not self._is_cm(X) or (npx_log2 >= 7 and gather is None)
+            assert not self._is_fm(X), "fragment-major buffers are read by the register-X attention tail only"
+        if gather is not None:
+            ld = gather.chunks * 32 + ld
+        # chunk-major weights [k / 32][n][32] for the ring kernels of the 128- / 256-row samples (the 16-row launches run the
+        # split-K small-launch kernel, which reads row-major weights)
+        w_cm = bool(self.use_cm and npx_log2 >= 7) or (gx is not None and self.prec == 1)
+        L = self._pack_layer(segs, npx_log2, rows, ld, in_cols, w_cm, chain=chain, pair_tabs=pair_tabs, pre_gather=pre_gather)
         if defer is not None:
-            return dict(W=Wd, epi=ed, epi_ptr=edp, n_cob=n_cob, k_pad=ld, flops=2 * rows * sum(int(s_["w"].size) for s_ in segs),
-                        wr=sum(rows * v[2] * v[1]["out"].element_size() for v in vec_list), wbytes=W.size * 4)
+            return dict(W=L.Wd, epi=L.epi, epi_ptr=L.epi_ptr, n_cob=L.n_cob, k_pad=ld, flops=L.flops, wr=L.written(), wbytes=L.W.size * 4)
         if gx is not None:
-            return self._emit_gx(gx, npx_log2, rows, ld, n_cob, Wd, edp, segs, W, vec_list, in_affine, pair_tabs, chain=chain)
-        if pair_fused is not None:  # SLIDE_OP_PAIR_FIRST: per-point GEMM + pair-table pass in one launch (_pair_first)
-            pf = pair_fused
-            assert npx_log2 == 4 and self.prec == 1 and in_affine is None and gather is None and gn_fin is None and not w_cm
-            assert X.dtype == self.adt and not self._is_cm(X)
-            fl = 2 * rows * sum(int(s_["w"].size) for s_ in segs)
-            self.flops += fl
-            return self._emit(make_op(OP_PAIR_FIRST, i=(rows, x_ld, ld, n_cob, pf["cob0"], pf["ld"], pf["K"]),
-                                      p=(X.data_ptr(), Wd.data_ptr(), edp, self.xyz.data_ptr(), pf["wa"].data_ptr(),
-                                         pf["wb"].data_ptr(), pf["ta"].data_ptr(), pf["tb"].data_ptr(), _dp(pf.get("nbr")),
-                                         _dp(pf.get("d2")), _dp(pf.get("w")), _dp(pf.get("vv_in")), _dp(pf.get("vv")))),
-                              flops=fl, nbytes=(rows * ld * 2 + W.size * 2, 2 * rows * pf["ld"] * 2 + rows * 32 * pf["cob0"] * 2),
-                              name="pair_first_kernel<%s>" % ("true" if pf["K"] == 8 else "false"))
+            return self._emit_gx(L, gx, npx_log2, in_affine, pair_tabs, chain)
+        if pair_fused is not None:
+            assert in_affine is None and gather is None and gn_fin is None
+            return self._emit_pair_first(L, X, npx_log2, pair_fused)
+        return self._emit_plain(L, X, npx_log2, in_affine, gather, gn_fin, pre_gather, pair_tabs)
+
+    def _emit_pair_first(self, L, X, npx_log2, pf):
+        """SLIDE_OP_PAIR_FIRST: per-point GEMM + pair-table pass in one launch (_pair_first)"""
+        rows, ld = L.rows, L.ld
+        assert npx_log2 == 4 and self.prec == 1 and not L.w_cm
+        assert X.dtype == self.adt and not self._is_cm(X)
+        self.flops += L.flops
+        return self._emit(make_op(OP_PAIR_FIRST, i=(rows, self._ldp(X), ld, L.n_cob, pf["cob0"], pf["ld"], pf["K"]),
+                                  p=(X.data_ptr(), L.Wd.data_ptr(), L.epi_ptr, self.xyz.data_ptr(), pf["wa"].data_ptr(),
+                                     pf["wb"].data_ptr(), pf["ta"].data_ptr(), pf["tb"].data_ptr(), _dp(pf.get("nbr")),
+                                     _dp(pf.get("d2")), _dp(pf.get("w")), _dp(pf.get("vv_in")), _dp(pf.get("vv")))),
+                          flops=L.flops, nbytes=(rows * ld * 2 + L.W.size * 2, 2 * rows * pf["ld"] * 2 + rows * 32 * pf["cob0"] * 2),
+                          name="pair_first_kernel<%s>" % ("true" if pf["K"] == 8 else "false"))
+
+    def _emit_plain(self, L, X, npx_log2, in_affine, gather, gn_fin, pre_gather, pair_tabs):
+        """SLIDE_OP_GEMM over a stored X (csrc/gemm_ring.hip run_gemm)"""
+        rows, ld, n_cob, Wd, w_cm = L.rows, L.ld, L.n_cob, L.Wd, L.w_cm
+        sc = None if in_affine is None else in_affine.scale
         assert X.dtype == self.adt
         # wide (128-channel) tiles only when the grid still covers the 256 CUs at least twice
         ntr = (rows + 255) // 256
@@ -441,12 +590,11 @@ class DenoiserEngine:
         # narrow launches: 32-channel tiles double the workgroups and halve each wave's epilogue while they still fit one round
         if (self.prec == 1 and self.use_glds and sc is None and npx_log2 >= 7 and ntr * n_cob <= int(os.environ.get('SLIDE_CBW1_TILES', '0'))):
             cbw = 1
-        fl = 2 * rows * sum(int(s["w"].size) for s in segs)
         esz = X.element_size()
-        rd = rows * ld * esz + W.size * esz + sum(rows * v[2] * esz for v in vec_list if v[1].get("residual") is not None)
-        rd += sum((rows >> max(v[1]["pre_add"][1], 0) if v[1]["pre_add"][1] >= 0 else rows >> npx_log2 << 4) * v[2] * esz
-                  for v in vec_list if v[1].get("pre_add") is not None)  # per-point tables (unique rows)
-        wr = sum(rows * v[2] * v[1]["out"].element_size() for v in vec_list)
+        rd = rows * ld * esz + L.W.size * esz + sum(rows * n * esz for sg, n in zip(L.segs, L.widths) if sg.get("residual") is not None)
+        rd += sum(self._pre_add_rows(sg["pre_add"], rows, npx_log2) * n * esz
+                  for sg, n in zip(L.segs, L.widths) if sg["pre_add"] is not None)  # per-point tables (unique rows)
+        wr = L.written()
         glds = int(self.use_glds and self.prec == 1 and (sc is None or npx_log2 >= 7))
         # X-stationary kernel (csrc/gemm_xs.hip: a workgroup keeps its input resident in LDS -- for the GATHERED first layers
         # of the SA / FP blocks only the 16-row point table + the coordinate chunk, 24 KB instead of a 144 KB X tile -- and
@@ -461,59 +609,63 @@ class DenoiserEngine:
         wfrag = None
         xs_mode = os.environ.get("SLIDE_XS", "")
         xs_levels = {7, 8} if xs_mode == "auto" else {int(v) for v in xs_mode.split(",") if v}
-        xs_lds = ((ld - (gather[3] * 32 if gather is not None else 0)) // 32) * 16384  # resident X rows (gathered chunks: 1 KB each)
+        xs_lds = ((ld - (gather.chunks * 32 if gather is not None else 0)) // 32) * 16384  # resident X rows (gathered chunks: 1 KB each)
         if (glds and npx_log2 in xs_levels and gn_fin is None and not (gather is not None and sc is not None)
                 and xs_lds + 20 * 1024 <= 160 * 1024):
             if xs_mode != "auto" or gather is not None or (npx_log2 == 8 and sc is None and n_cob >= 16 and xs_lds > 96 * 1024):
                 wfrag = Wd  # (selects the kernel; it reads the same row-major weights)
                 cbw = 4 if n_cob >= 4 and os.environ.get("SLIDE_XS_CBW", "2") == "4" else 2
-        gtab = None if gather is None else self._cm_copy.get(gather[0].data_ptr(), gather[0])  # chunk-major copy: g_ldf == 32
-        assert wfrag is None or gtab is None or gtab is gather[0]
-        gf = (0.0, 0.0, 0.0) if gather is None else (float(gather[3]), float(32 if gtab is not gather[0] else gather[0].shape[1]),
-                                                     float({8: 3, 16: 4}[gather[2]]))
+        gtab = None if gather is None else self._cm_copy.get(gather.table.data_ptr(), gather.table)  # chunk-major copy: g_ldf == 32
+        assert wfrag is None or gtab is None or gtab is gather.table
+        gf = (0.0, 0.0, 0.0) if gather is None else (float(gather.chunks), float(32 if gtab is not gather.table else gather.table.shape[1]),
+                                                     float({8: 3, 16: 4}[gather.K]))
         knob = self.glds_nst
         assert wfrag is None or not (w_cm or self._is_cm(X))
         if wfrag is not None and os.environ.get("SLIDE_XS_OCC"):
             knob = 10 + int(os.environ["SLIDE_XS_OCC"])  # cap the workgroups per CU of the X-stationary kernel (A/B timing)
-        has_pair = any(v[1].get("res_pair") is not None for v in vec_list)  # -> the kernels compiled with the PAIR residual
+        has_pair = any(sg["res_pair"] is not None for sg in L.segs)  # -> the kernels compiled with the PAIR residual
         # (a per-point layer of a split plan: _merge_pp may fold it into a SLIDE_OP_PP_STAGE launch, from its float weights)
         pp = (self.use_gxs and npx_log2 == 4 and gather is None and gn_fin is None and pre_gather is None and wfrag is None and
-              not any(v[1].get("pre_add") is not None for v in vec_list))
+              not any(sg["pre_add"] is not None for sg in L.segs))
         nbr, d2, wts = pair_tabs or (None, None, None)  # PAIR_NBR residual: p[9] = neighbour table, p[12] / p[13] = squared distances / weights
         assert pair_tabs is None or (gather is None and pre_gather is None)
-        self.flops += fl
-        return self._emit(make_op(OP_GEMM, i=(rows, x_ld, ld, n_cob, npx_log2, in_bs, self.prec, cbw, glds | (2 if w_cm else 0) | (4 if has_pair else 0), knob),
+        self.flops += L.flops
+        return self._emit(make_op(OP_GEMM, i=(rows, self._ldp(X), ld, n_cob, npx_log2, 0 if in_affine is None else in_affine.bs, self.prec, cbw,
+                                              glds | (2 if w_cm else 0) | (4 if has_pair else 0), knob),
                                   f=(-1.0 if self.persistent == 2 else float(os.environ.get('SLIDE_STAGGER_US', '0')),) + gf,
-                                  p=(X.data_ptr(), Wd.data_ptr(), edp, None if sc is None else sc.data_ptr() + 4 * aff_off,
-                                     None if sh is None else sh.data_ptr() + 4 * aff_off, None, _dp(gn_fin),
+                                  p=self._affine_ptrs(X.data_ptr(), Wd.data_ptr(), L.epi_ptr, in_affine) + (None, _dp(gn_fin),
                                      self._sched().data_ptr() if self.persistent else None, _dp(gtab),
-                                     _dp(gather[1] if gather is not None else pre_gather if pair_tabs is None else nbr),
+                                     _dp(gather.nbr if gather is not None else pre_gather if pair_tabs is None else nbr),
                                      _dp(wfrag), None, _dp(d2), _dp(wts))),
-                          flops=fl, nbytes=(rd, wr), w16=W if pp else None)  # nbytes: algorithmic HBM bytes (read, written)
+                          flops=L.flops, nbytes=(rd, wr), w16=L.W if pp else None)  # nbytes: algorithmic HBM bytes (read, written)
+
+    @staticmethod
+    def _affine_ptrs(x, w, epi, in_affine):
+        """p[0..4] of the GEMM ops: input, weights, descriptors, the input affine's scale and shift rows"""
+        if in_affine is None:
+            return (x, w, epi, None, None)
+        return (x, w, epi, in_affine.scale.data_ptr() + 4 * in_affine.off, in_affine.shift.data_ptr() + 4 * in_affine.off)
 
     @staticmethod
     def _split1_ok(*ws):
         """the single-accumulator split kernels (csrc/gemm_gxs.hip) scale the weight's high term by 2^11 in fp16: |w| < 32"""
         return all(float(np.abs(w).max()) < 31.0 for w in ws if w.size)
 
-    def _emit_gx(self, gx, npx_log2, rows, ld, n_cob, Wd, edp, segs, W, vec_list, in_affine, pair_tabs, chain=None):
+    def _emit_gx(self, L, gx, npx_log2, in_affine, pair_tabs, chain=None):
         """SLIDE_OP_GEMM_GX (include/slide_engine.h): gx = dict(ta, tb (fp16 tables [B*16][t_ld]), coff (first table column),
-        k_pad, rows, mode, add=(tensor, offset, per-sample stride, idx tensor or None, idx stride) or None, vv = per-sample
-        (vd | vw) fp32 [B][2][t_ld] of the 8-neighbour samples or None); pair_tabs = (neighbour, d2, w tables) for those"""
+        k_pad, rows, mode, add (AddVec) or None, vv = per-sample (vd | vw) fp32 [B][2][t_ld] of the 8-neighbour samples or None);
+        pair_tabs = (neighbour, d2, w tables) for those"""
+        rows, ld, n_cob = L.rows, L.ld, L.n_cob
         ta, tb, coff = gx["ta"], gx["tb"], gx["coff"]
         tes = ta.element_size()
         assert ta.dtype == (torch.float16 if self.prec == 1 else torch.float32) and ta.shape == tb.shape and coff % 8 == 0
         assert ta.shape[1] >= coff + ld
-        fl = 2 * rows * sum(int(s_["w"].size) for s_ in segs)
-        rd = 2 * (rows >> npx_log2) * 16 * ld * tes + W.size * tes
-        wr = sum(rows * v[2] * v[1]["out"].element_size() for v in vec_list if v[1]["out"] is not None)
+        fl = L.flops
+        rd = 2 * (rows >> npx_log2) * 16 * ld * tes + L.W.size * tes
+        wr = L.written()
         if chain is not None:  # the chained layer's work rides on this launch
             fl += chain["flops"]; rd += chain["wbytes"]; wr += chain["wr"]
-        sc = sh = None
-        in_bs = aff_off = 0
-        if in_affine is not None:
-            sc, sh, aff_off, in_bs = in_affine
-        add = gx.get("add")
+        add = _rec(AddVec, gx.get("add"))
         vv = gx.get("vv")
         assert (npx_log2 == 7) == (pair_tabs is not None)
         # (the launcher's choice, csrc/gemm_gx.hip: mode-1 layers run 256 x 64 tiles when three workgroups fit a CU's LDS)
@@ -537,7 +689,7 @@ class DenoiserEngine:
             nst = 3 if shm128(3) <= 80 * 1024 else 2
         name = "gemm_gx_%skernel<%d, %d, %d>" % (("", "n64_", "n64w_")[n64], npx_log2, nst, gx["mode"])
         if self.prec == 2:  # split arithmetic on float tables: csrc/gemm_gxs.hip (256 x 64 tiles)
-            if not self._split1_ok(W):
+            if not self._split1_ok(L.W):
                 raise SlideHipError("a weight of magnitude >= 31 in a generated-X layer: the split pair-decomposition kernels scale the "
                                     "weights' high terms by 2^11 in fp16 -- build this plan with SLIDE_GXS=0")
             n64 = 3
@@ -546,30 +698,32 @@ class DenoiserEngine:
             assert chain is None or (npx_log2 == 8 and gx["mode"] == 0 and n_cob <= 2 and chain["k_pad"] == n_cob * 32)
         self.flops += fl
         return self._emit(make_op(OP_GEMM_GX,
-                                  i=(rows, ta.shape[1], ld, n_cob, npx_log2, in_bs, gx["mode"], 0 if add is None else add[2],
-                                     0 if add is None else add[4], 0 if vv is None else 2 * vv.shape[2]),
+                                  i=(rows, ta.shape[1], ld, n_cob, npx_log2, 0 if in_affine is None else in_affine.bs, gx["mode"],
+                                     0 if add is None else add.bs, 0 if add is None else add.idx_stride, 0 if vv is None else 2 * vv.shape[2]),
                                   f=(float(n64),) + ((float(chain["n_cob"]), float(chain["k_pad"])) if chain is not None else ()),
-                                  p=(ta.data_ptr() + tes * coff, Wd.data_ptr(), edp,
-                                     None if sc is None else sc.data_ptr() + 4 * aff_off,
-                                     None if sh is None else sh.data_ptr() + 4 * aff_off,
-                                     tb.data_ptr() + tes * coff,
-                                     None if add is None else add[0].data_ptr() + 4 * add[1],
-                                     None if add is None else _dp(add[3])) + tuple(_dp(t) for t in pair_tabs or (None,) * 3) +
+                                  p=self._affine_ptrs(ta.data_ptr() + tes * coff, L.Wd.data_ptr(), L.epi_ptr, in_affine) +
+                                    (tb.data_ptr() + tes * coff,
+                                     None if add is None else add.vec.data_ptr() + 4 * add.off,
+                                     None if add is None else _dp(add.idx)) + tuple(_dp(t) for t in pair_tabs or (None,) * 3) +
                                     (None if vv is None else vv.data_ptr() + 4 * coff,
                                      None if chain is None else chain["W"].data_ptr(), None if chain is None else chain["epi_ptr"])),
                           flops=fl, nbytes=(rd, wr), name=name)
 
     # ------------------------------------------------------------------ blocks
+    def _conv_gn_relu(self, conv, gn, **kw):
+        """segment of a convolution + GroupNorm + ReLU (state-dict prefixes of the two modules); kw: further keys of the segment"""
+        sd = self.sd
+        return dict(w=self._w(conv + ".weight"), bias=sd[conv + ".bias"], mode=EPI_NORM, flags=F_POST_RELU,
+                    layout=gn_layout(sd[conv + ".weight"].shape[0]), gn=(sd[gn + ".weight"], sd[gn + ".bias"]), **kw)
+
     def _mlp_segments(self, pfx, tvec, cvec, out1, res_out):
         """first_mlp + res_connect segments of Mlp_plus_t_emb (pointnet2_modules.py:119-176) sharing one input"""
         sd = self.sd
         c1 = sd[pfx + ".first_mlp.0.weight"].shape[0]
-        first = dict(w=self._w(pfx + ".first_mlp.0.weight"), bias=sd[pfx + ".first_mlp.0.bias"], mode=EPI_NORM,
-                     flags=F_POST_RELU, layout=gn_layout(c1), out=out1,
-                     gn=(sd[pfx + ".first_mlp.1.group_norm.weight"], sd[pfx + ".first_mlp.1.group_norm.bias"]))
+        first = self._conv_gn_relu(pfx + ".first_mlp.0", pfx + ".first_mlp.1.group_norm", out=out1)
         if (pfx + ".fc.weight") in sd:
-            first["addvec"] = (tvec, self._tvec_off(pfx + ".fc", c1), self._t_bs,
-                               None if self.per_sample_t else self.t_dev, self._n_fc)
+            first["addvec"] = AddVec(tvec, self._tvec_off(pfx + ".fc", c1), self._t_bs,
+                                     None if self.per_sample_t else self.t_dev, self._n_fc)
         assert (pfx + ".res_connect.weight") in sd, "identity res_connect (mlp_spec[0]==mlp_spec[-1]) not planned"
         res = dict(w=self._w(pfx + ".res_connect.weight"), bias=sd[pfx + ".res_connect.bias"], mode=EPI_RAW, out=res_out)
         return first, res
@@ -581,36 +735,31 @@ class DenoiserEngine:
         sd = self.sd
         rows = h1.shape[0] if pair is None else pair["rows"]
 
-        def first_gemm(seg_):
+        def first_gemm(seg_, **kw):
             if pair is None:
                 return self._gemm(h1, npx_log2, [seg_])
             lay1 = pair["lay1"]
-            self._gemm(None, npx_log2, [seg_], in_cols=lay1[0],
-                       gx=dict(ta=pair["ta"], tb=pair["tb"], coff=pair["off1"], k_pad=ru(lay1[1]), rows=rows, mode=0,
-                               add=pair["add1"], vv=pair["vv"]), pair_tabs=pair["tabs"])
+            self._gemm(None, npx_log2, [seg_], in_cols=lay1.index,
+                       gx=dict(ta=pair["ta"], tb=pair["tb"], coff=pair["off1"], k_pad=ru(lay1.width), rows=rows, mode=0,
+                               add=pair["add1"], vv=pair["vv"]), pair_tabs=pair["tabs"], **kw)
 
         def with_res(seg_):
             if pair is None:
                 seg_["residual"] = r
             else:
-                seg_["res_pair"] = (pair["ta"], pair["tb"], pair["offr"], pair["rvv"])
+                seg_["res_pair"] = ResPair(pair["ta"], pair["tb"], pair["offr"], pair["rvv"])
             return seg_
         has_rest = (pfx + ".rest_mlp.0.weight") in sd
         c2 = sd[pfx + ".second_mlp.0.weight"].shape[0]
-        seg = dict(w=self._w(pfx + ".second_mlp.0.weight"), bias=sd[pfx + ".second_mlp.0.bias"], mode=EPI_NORM,
-                   flags=F_POST_RELU, layout=gn_layout(c2),
-                   gn=(sd[pfx + ".second_mlp.1.group_norm.weight"], sd[pfx + ".second_mlp.1.group_norm.bias"]))
+        seg = self._conv_gn_relu(pfx + ".second_mlp.0", pfx + ".second_mlp.1.group_norm")
         if (pfx + ".fc_condition.weight") in sd:
-            seg["addvec"] = (cvec, self._cvec_off(pfx + ".fc_condition", c2), self._c_bs, None, 0)
+            seg["addvec"] = AddVec(cvec, self._cvec_off(pfx + ".fc_condition", c2), self._c_bs)
         if has_rest and pair is not None and self._sa_chain(pfx, npx_log2, pair, cvec, seg, final_out, final_coff):
             return
         if has_rest:
-            c3 = sd[pfx + ".rest_mlp.0.weight"].shape[0]
-            assert np.array_equal(gn_layout(c2)[0], np.arange(c2)), "second_mlp width with padded GroupNorm groups"
-            seg3 = with_res(dict(w=self._w(pfx + ".rest_mlp.0.weight"), bias=sd[pfx + ".rest_mlp.0.bias"], mode=EPI_NORM,
-                                 flags=F_POST_RELU, layout=gn_layout(c3), out=final_out, out_coff=final_coff,
-                                 gn=(sd[pfx + ".rest_mlp.1.group_norm.weight"], sd[pfx + ".rest_mlp.1.group_norm.bias"])))
-        if (has_rest and pair is not None and self.use_gxs and npx_log2 == 8 and ru(gn_layout(c2)[1]) <= 64
+            assert gn_layout(c2).unpermuted, "second_mlp width with padded GroupNorm groups"
+            seg3 = with_res(self._conv_gn_relu(pfx + ".rest_mlp.0", pfx + ".rest_mlp.1.group_norm", out=final_out, out_coff=final_coff))
+        if (has_rest and pair is not None and self.use_gxs and npx_log2 == 8 and ru(gn_layout(c2).width) <= 64
                 and os.environ.get("SLIDE_GXS_CHAIN", "1") != "0"):
             # split plans (round 5): second_mlp -> rest_mlp of an SA block in ONE launch -- h2 stays in the generated-X kernel's
             # accumulators and feeds rest_mlp's contraction from there (csrc/gemm_gxs.hip, CHAIN); needs every channel of h2 in
@@ -618,10 +767,7 @@ class DenoiserEngine:
             if self._split1_ok(seg3["w"]):
                 layer2 = self._gemm(None, npx_log2, [seg3], pair_tabs=pair["tabs"], defer=dict(rows=rows, k_pad=ru(c2)))
                 seg["out"] = None
-                lay1 = pair["lay1"]
-                self._gemm(None, npx_log2, [seg], in_cols=lay1[0],
-                           gx=dict(ta=pair["ta"], tb=pair["tb"], coff=pair["off1"], k_pad=ru(lay1[1]), rows=rows, mode=0,
-                                   add=pair["add1"], vv=pair["vv"]), pair_tabs=pair["tabs"], chain=layer2)
+                first_gemm(seg, chain=layer2)
                 return
         if has_rest:
             h2 = self._buf(rows, c2, cm=npx_log2 >= 7)
@@ -644,9 +790,8 @@ class DenoiserEngine:
         c2 = sd[pfx + ".second_mlp.0.weight"].shape[0]
         c3 = sd[pfx + ".rest_mlp.0.weight"].shape[0]
         l1, l2, l3 = gn_layout(c1), gn_layout(c2), gn_layout(c3)
-        ident = lambda l, c: np.array_equal(l[0], np.arange(c)) and l[1] == c and l[2] == c
-        return bool(c2 in (128, 256) and c3 % 256 == 0 and c1 % 64 == 0 and ident(l1, c1) and ident(l2, c2) and ident(l3, c3)
-                    and l2[3] in (4, 8, 16) and l3[3] in (4, 8, 16))
+        return bool(c2 in (128, 256) and c3 % 256 == 0 and c1 % 64 == 0 and l1.identity and l2.identity and l3.identity
+                    and l2.gs in (4, 8, 16) and l3.gs in (4, 8, 16))
 
     def _sa_chain(self, pfx, npx_log2, pair, cvec, seg, final_out, final_coff):
         """second_mlp -> rest_mlp of an SA block as ONE launch (SLIDE_OP_SA_CHAIN, csrc/gemm_gx.hip: h2 stays in registers).
@@ -657,31 +802,30 @@ class DenoiserEngine:
         w1, w2 = self._w(pfx + ".second_mlp.0.weight"), self._w(pfx + ".rest_mlp.0.weight")
         c2, c1 = w1.shape
         c3 = w2.shape[0]
-        lay1, l2, l3 = pair["lay1"], gn_layout(c2), gn_layout(c3)
-        assert np.array_equal(lay1[0], np.arange(c1)) and lay1[1] == c1
+        lay1, l2, l3 = GnLayout(*pair["lay1"]), gn_layout(c2), gn_layout(c3)
+        assert lay1.unpermuted and len(lay1.index) == c1 and lay1.width == c1
         if not (self._is_cm(final_out) and final_coff == 0 and final_out.shape[1] == c3):
             return False
-        cm = lambda w: np.ascontiguousarray(w.reshape(w.shape[0], -1, 32).transpose(1, 0, 2))
-        vec = lambda b_, g_, bt_: np.stack([b_, g_, bt_]).astype(np.float32)
-        d = [self.A.put(cm(w1), torch.float16), self.A.put(cm(w2), torch.float16),
-             self.A.put(vec(sd[pfx + ".second_mlp.0.bias"], *seg["gn"])),
-             self.A.put(vec(sd[pfx + ".rest_mlp.0.bias"], sd[pfx + ".rest_mlp.1.group_norm.weight"],
-                            sd[pfx + ".rest_mlp.1.group_norm.bias"]))]
-        add0, add1 = pair["add1"], seg.get("addvec")
+        # (the kernel takes every channel where it logically is)
+        d = [self.A.put(chunk_major(w1), torch.float16), self.A.put(chunk_major(w2), torch.float16),
+             self.A.put(epi_vectors(GnLayout.plain(c2), c2, sd[pfx + ".second_mlp.0.bias"], seg["gn"])),
+             self.A.put(epi_vectors(GnLayout.plain(c3), c3, sd[pfx + ".rest_mlp.0.bias"],
+                                    (sd[pfx + ".rest_mlp.1.group_norm.weight"], sd[pfx + ".rest_mlp.1.group_norm.bias"])))]
+        add0, add1 = _rec(AddVec, pair["add1"]), _rec(AddVec, seg.get("addvec"))
         ta, tb = pair["ta"], pair["tb"]
         rows = B * 256
         fl = 2 * rows * (w1.size + w2.size)
         self.flops += fl
         self._emit(make_op(OP_SA_CHAIN,
-                           i=(B, ta.shape[1], c1, c2, c3, l2[3], l3[3], 0 if add0 is None else add0[4], 0 if add0 is None else add0[2],
-                              0 if add1 is None else add1[2]),
-                           f=(1.0 / (l2[4] * 256), 1.0 / (l3[4] * 256), 1.0 if self._is_fm(final_out) else 0.0),
+                           i=(B, ta.shape[1], c1, c2, c3, l2.gs, l3.gs, 0 if add0 is None else add0.idx_stride,
+                              0 if add0 is None else add0.bs, 0 if add1 is None else add1.bs),
+                           f=(1.0 / (l2.gs_logical * 256), 1.0 / (l3.gs_logical * 256), 1.0 if self._is_fm(final_out) else 0.0),
                            p=(ta.data_ptr() + 2 * pair["off1"], tb.data_ptr() + 2 * pair["off1"],
                               ta.data_ptr() + 2 * pair["offr"], tb.data_ptr() + 2 * pair["offr"],
                               d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
-                              None if add0 is None else add0[0].data_ptr() + 4 * add0[1],
-                              None if add0 is None or add0[3] is None else add0[3].data_ptr(),
-                              None if add1 is None else add1[0].data_ptr() + 4 * add1[1], final_out.data_ptr())),
+                              None if add0 is None else add0.vec.data_ptr() + 4 * add0.off,
+                              None if add0 is None else _dp(add0.idx),
+                              None if add1 is None else add1.vec.data_ptr() + 4 * add1.off, final_out.data_ptr())),
                    flops=fl, nbytes=(2 * B * 16 * (c1 + c3) * 2 + (w1.size + w2.size) * 2, rows * c3 * 2),
                    name="sa_chain_kernel<%d>" % (c2 // 32))
         return True
@@ -697,7 +841,7 @@ class DenoiserEngine:
         Tq = self.A.zeros(B * 16, ru(C1), dtype=self.adt)
         ssum, ssq = self.A.zeros(B, ldT), self.A.zeros(B, ldT)
         qseg = dict(w=self._w(apfx + ".feat_conv.weight"), bias=sd[apfx + ".feat_conv.bias"], mode=EPI_STATS,
-                    flags=F_PRE_RELU, out=Tq, stats=(ssum, ssq, 0, float(K)))
+                    flags=F_PRE_RELU, out=Tq, stats=Stats(ssum, ssq, 0, float(K)))
         return dict(Tq=Tq, ssum=ssum, ssq=ssq, qseg=qseg)
 
     def _pair_first(self, npx_log2, K, feat_in, C, segs, coords, fin=None, lead_segs=()):
@@ -709,13 +853,8 @@ class DenoiserEngine:
         channels); coords: dict(rel, abs, ctr = first column of each 3-channel coordinate group, d2 / w = column or None).
         Returns the context the consumers (generated-X GEMMs, PAIR residuals) take."""
         B = self.B
-        offs, ysegs, off = [], [], 0
-        for sg in segs:
-            lay = sg.get("layout")
-            Op = ru(sg["w"].shape[0] if lay is None else lay[1])
-            offs.append(off)
-            off += Op
-        ldy = off
+        ysegs = []
+        offs, ldy = seg_offsets(segs)
         # SLIDE_PAIR_FUSED (default on): the per-point GEMM and the pair-table pass as ONE launch (SLIDE_OP_PAIR_FIRST,
         # csrc/gemm_ring.hip pair_first_kernel) -- y never goes through memory; bit-identical to the two-launch form
         fused = fin is None and self.prec == 1 and self.use_glds and os.environ.get("SLIDE_PAIR_FUSED", "1") != "0"
@@ -723,21 +862,19 @@ class DenoiserEngine:
         wa, wb, vv_in = np.zeros((ldy, 4), np.float32), np.zeros((ldy, 4), np.float32), np.zeros((2, ldy), np.float32)
         psegs = []
         for sg, o_ in zip(segs, offs):
-            lay = sg.get("layout")
+            lay = _rec(GnLayout, sg.get("layout"))
             w = sg["w"]
-            oidx = (np.arange(w.shape[0]) if lay is None else lay[0]) + o_
+            oidx = (np.arange(w.shape[0]) if lay is None else lay.index) + o_
             ysegs.append(dict(w=w[:, :C], bias=sg.get("bias"), mode=EPI_RAW, out=Y, out_coff=o_,
-                              layout=None if lay is None else (lay[0], lay[1], 0, 1, 1)))
+                              layout=None if lay is None else lay.raw()))
             rel, ab, ctr = (w[:, coords[k_]:coords[k_] + 3] for k_ in ("rel", "abs", "ctr"))
             wa[oidx, :3] = rel + ab
             wb[oidx, :3] = ctr - rel
             if coords.get("d2") is not None:
                 vv_in[0, oidx] = w[:, coords["d2"]]
                 vv_in[1, oidx] = w[:, coords["w"]]
-            ps = dict(sg)
-            ps["w"] = w[:, :0]  # descriptors only: mode / flags / GroupNorm parameters / statistics
-            ps["out"] = None
-            psegs.append(ps)
+            # descriptors only: mode / flags / GroupNorm parameters / statistics
+            psegs.append(dict({k_: sg[k_] for k_ in ("mode", "flags", "layout", "gn", "stats") if k_ in sg}, w=w[:, :0], out=None))
         assert sum(3 for _ in ("rel", "abs", "ctr")) + (2 if coords.get("d2") is not None else 0) + C == segs[0]["w"].shape[1]
         tdt = torch.float16 if self.prec == 1 else torch.float32  # (split plans: float tables)
         ta = self.A.zeros(B * 16, ldy, dtype=tdt)
@@ -757,61 +894,26 @@ class DenoiserEngine:
                     assert fs.get(k_) is None or k_ == "addvec"
                 fs.pop("addvec", None)  # (first_mlp's t-embedding rows are added by the consumers, after the ReLU)
                 fsegs.append(fs)
-            lead_cobs = sum(ru(sg["w"].shape[0] if sg.get("layout") is None else sg["layout"][1]) for sg in lead_segs) // 32
             self._gemm(feat_in, 4, list(lead_segs) + fsegs,
-                       pair_fused=dict(cob0=lead_cobs, ld=ldy, K=K, wa=d[0], wb=d[1], ta=ta, tb=tb,
+                       pair_fused=dict(cob0=seg_offsets(lead_segs)[1] // 32, ld=ldy, K=K, wa=d[0], wb=d[1], ta=ta, tb=tb,
                                        nbr=self.kidx if fp else None, d2=self.kd2 if fp else None, w=self.kw if fp else None,
                                        vv_in=d[2] if fp else None, vv=vv))
-            return dict(ta=ta, tb=tb, vv=vv, offs=offs, ldy=ldy, rows=B * 16 * K, vv_in=vv_in,
-                        tabs=(self.kidx, self.kd2, self.kw) if fp else None)
-        # (lead_segs: other per-point GEMM segments over the same table -- the attention queries -- ride on this launch)
-        self._gemm(feat_in, 4, list(lead_segs) + ysegs)
-        ed = self._epi_only(psegs, 1 << npx_log2)
-        # loop-invariant when the coordinates are a fixed condition?  No: y changes every step.
-        v2 = ldy <= 2048 and (os.environ.get("SLIDE_PAIR_NORM_V2", "0") != "0" or self.prec != 1)
-        assert (fin is None or v2) and (self.prec == 1 or v2)
-        self._emit(make_op(OP_PAIR_NORM, i=(B, ldy, K, 2 if v2 else 1, int(self.prec != 1)),
-                           p=(Y.data_ptr(), self.xyz.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), ed.data_ptr(),
-                              ta.data_ptr(), tb.data_ptr(), self.kidx.data_ptr() if fp else None,
-                              self.kd2.data_ptr() if fp else None, self.kw.data_ptr() if fp else None,
-                              d[2].data_ptr() if fp else None, vv.data_ptr() if fp else None,
-                              _dp(fin))),
-                   name="pair_norm2_kernel<%s, %s>" % ("true" if fp else "false", "_Float16" if self.prec == 1 else "float"))
+        else:
+            # (lead_segs: other per-point GEMM segments over the same table -- the attention queries -- ride on this launch)
+            self._gemm(feat_in, 4, list(lead_segs) + ysegs)
+            ed = self._epi_only(psegs, 1 << npx_log2)
+            # loop-invariant when the coordinates are a fixed condition?  No: y changes every step.
+            v2 = ldy <= 2048 and (os.environ.get("SLIDE_PAIR_NORM_V2", "0") != "0" or self.prec != 1)
+            assert (fin is None or v2) and (self.prec == 1 or v2)
+            self._emit(make_op(OP_PAIR_NORM, i=(B, ldy, K, 2 if v2 else 1, int(self.prec != 1)),
+                               p=(Y.data_ptr(), self.xyz.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), ed.data_ptr(),
+                                  ta.data_ptr(), tb.data_ptr(), self.kidx.data_ptr() if fp else None,
+                                  self.kd2.data_ptr() if fp else None, self.kw.data_ptr() if fp else None,
+                                  d[2].data_ptr() if fp else None, vv.data_ptr() if fp else None,
+                                  _dp(fin))),
+                       name="pair_norm2_kernel<%s, %s>" % ("true" if fp else "false", "_Float16" if self.prec == 1 else "float"))
         return dict(ta=ta, tb=tb, vv=vv, offs=offs, ldy=ldy, rows=B * 16 * K, vv_in=vv_in,
                     tabs=(self.kidx, self.kd2, self.kw) if fp else None)
-
-    def _epi_only(self, segs, npx):
-        """device array of SlideEpi descriptors (one per 32 physical channels) carrying only what SLIDE_OP_PAIR_NORM reads:
-        mode, flags, GroupNorm layout / parameters, statistics pointers"""
-        blocks = []
-        for sg in segs:
-            lay = sg.get("layout")
-            O = sg["w"].shape[0]
-            oidx, Op, n_norm_p, gs_p, gs_l = (np.arange(O), O, 0, 1, 1) if lay is None else lay
-            Opad = ru(Op)
-            vec = np.zeros((2, Opad), np.float32)
-            if sg.get("gn") is not None:
-                gam, bet = sg["gn"]
-                vec[0, oidx[:gam.shape[0]]] = gam
-                vec[1, oidx[:gam.shape[0]]] = bet
-            vd = self.A.put(vec)
-            for j in range(Opad // 32):
-                e = SlideEpi()
-                e.mode = sg.get("mode", EPI_RAW)
-                e.flags = sg.get("flags", 0)
-                e.gs = gs_p
-                e.n_norm = int(min(32, max(0, n_norm_p - 32 * j)))
-                e.inv_count = 1.0 / (gs_l * npx)
-                e.gamma = vd.data_ptr() + 4 * (32 * j)
-                e.beta = vd.data_ptr() + 4 * (Opad + 32 * j)
-                if sg.get("stats") is not None:
-                    ssum, ssq, scoff, scale = sg["stats"]
-                    e.stats_sum = ssum.data_ptr() + 4 * (scoff + 32 * j)
-                    e.stats_sq = ssq.data_ptr() + 4 * (scoff + 32 * j)
-                    e.stats_bs = ssum.shape[1]
-                    e.stats_scale = scale
-                blocks.append(bytes(e))
-        return self.A.put(np.frombuffer(b"".join(blocks), dtype=np.uint8).copy())
 
     def _body_shape(self, mpfx, apfx, npx_log2):
         """(rest, nb1, nbm, nbu) if SLIDE_OP_BLOCK_BODY has an instantiation for this block's widths, else None"""
@@ -828,11 +930,11 @@ class DenoiserEngine:
         inter = sd[apfx + ".weight_conv.2.weight"].shape[0]
         cout = sd[apfx + ".weight_conv.5.weight"].shape[0]
         lay_u = gn_layout(inter)
-        n_u = ru(lay_u[1])
-        ident = lambda c: (lambda l: np.array_equal(l[0], np.arange(c)) and l[1] == c and l[2] == c)(gn_layout(c))
-        okgs = lambda c: gn_layout(c)[3] in (4, 8, 16)
-        if not (ident(c1) and ident(c2) and ident(n_mo) and ident(cout) and okgs(c2) and okgs(n_mo) and lay_u[3] in (4, 8, 16)
-                and c1 % 32 == 0 and n_mo % 32 == 0 and cout % 64 == 0 and gn_layout(cout)[3] <= 32):
+        n_u = ru(lay_u.width)
+        ident = lambda c: gn_layout(c).identity
+        okgs = lambda c: gn_layout(c).gs in (4, 8, 16)
+        if not (ident(c1) and ident(c2) and ident(n_mo) and ident(cout) and okgs(c2) and okgs(n_mo) and lay_u.gs in (4, 8, 16)
+                and c1 % 32 == 0 and n_mo % 32 == 0 and cout % 64 == 0 and gn_layout(cout).gs <= 32):
             return None
         shape = (npx_log2, rest, (c2 // 32) if rest else 0, n_mo // 32, n_u // 32)
         # ((7, False, 0, 8, 8) -- FP1 -- was built and measured slower than its three separate launches: one wave per SIMD)
@@ -849,13 +951,11 @@ class DenoiserEngine:
         apfx = body["apfx"]
         npx = 1 << npx_log2
         rest = (mpfx + ".rest_mlp.0.weight") in sd
-        cm = lambda w: np.ascontiguousarray(w.reshape(w.shape[0], -1, 32).transpose(1, 0, 2))
-        vec3 = lambda n, lay, b_, g_, bt_: (lambda v: (v.__setitem__((0, lay[0]), b_), v.__setitem__((1, lay[0][:g_.shape[0]]), g_),
-                                                    v.__setitem__((2, lay[0][:bt_.shape[0]]), bt_), v)[-1])(np.zeros((3, n), np.float32))
+        vec3 = lambda n, lay, conv, gn: epi_vectors(lay, n, sd[conv + ".bias"], (sd[gn + ".weight"], sd[gn + ".bias"]))
         a = BodyArgs()
         keep = []
         slots = []
-        put16 = lambda w: (lambda t: (keep.append(t), t)[1])(self.A.put(cm(w), torch.float16))
+        put16 = lambda w: (lambda t: (keep.append(t), t)[1])(self.A.put(chunk_major(w), torch.float16))
         putf = lambda v: (lambda t: (keep.append(t), t)[1])(self.A.put(np.ascontiguousarray(v, np.float32)))
 
         # slot geometry (csrc/block_body.hip): eight-wave form (16 x 16-row samples) 128-row slabs / 64-channel column blocks,
@@ -876,9 +976,8 @@ class DenoiserEngine:
         if rest:
             W1 = put16(w_sec)
             slab_slots(W1, c2, c1)
-            a.vec1 = putf(vec3(c2, lay2, sd[mpfx + ".second_mlp.0.bias"], sd[mpfx + ".second_mlp.1.group_norm.weight"],
-                               sd[mpfx + ".second_mlp.1.group_norm.bias"])).data_ptr()
-            a.n1, a.gs1, a.inv1 = c2, lay2[3], 1.0 / (lay2[4] * npx)
+            a.vec1 = putf(vec3(c2, lay2, mpfx + ".second_mlp.0", mpfx + ".second_mlp.1.group_norm")).data_ptr()
+            a.n1, a.gs1, a.inv1 = c2, lay2.gs, 1.0 / (lay2.gs_logical * npx)
             if (mpfx + ".fc_condition.weight") in sd:
                 a.add1 = cvec.data_ptr() + 4 * self._cvec_off(mpfx + ".fc_condition", c2)
                 a.add1_bs = self._c_bs
@@ -887,38 +986,35 @@ class DenoiserEngine:
             laym = gn_layout(n_mo)
             Wm = put16(w_m)
             slab_slots(Wm, n_mo, c2)
-            a.vecm = putf(vec3(n_mo, laym, sd[mpfx + ".rest_mlp.0.bias"], sd[mpfx + ".rest_mlp.1.group_norm.weight"],
-                               sd[mpfx + ".rest_mlp.1.group_norm.bias"])).data_ptr()
+            a.vecm = putf(vec3(n_mo, laym, mpfx + ".rest_mlp.0", mpfx + ".rest_mlp.1.group_norm")).data_ptr()
             fl += w_sec.size + w_m.size
         else:
             n_mo, laym = c2, lay2
             Wm = put16(w_sec)
             slab_slots(Wm, n_mo, c1)
-            a.vecm = putf(vec3(n_mo, laym, sd[mpfx + ".second_mlp.0.bias"], sd[mpfx + ".second_mlp.1.group_norm.weight"],
-                               sd[mpfx + ".second_mlp.1.group_norm.bias"])).data_ptr()
+            a.vecm = putf(vec3(n_mo, laym, mpfx + ".second_mlp.0", mpfx + ".second_mlp.1.group_norm")).data_ptr()
             if (mpfx + ".fc_condition.weight") in sd:
                 a.addm = cvec.data_ptr() + 4 * self._cvec_off(mpfx + ".fc_condition", c2)
                 a.addm_bs = self._c_bs
             fl += w_sec.size
-        a.n_mo, a.gsm, a.invm = n_mo, laym[3], 1.0 / (laym[4] * npx)
+        a.n_mo, a.gsm, a.invm = n_mo, laym.gs, 1.0 / (laym.gs_logical * npx)
         # keys -> u
         lay_u = body["lay_u"]
-        n_u = ru(lay_u[1])
+        n_u = ru(lay_u.width)
         C1, C2p = body["C1"], body["C2p"]
         w2k = body["w2"][:, C1:]
         wk = np.zeros((n_u, C2p), np.float32)
-        wk[lay_u[0], :w2k.shape[1]] = w2k
+        wk[lay_u.index, :w2k.shape[1]] = w2k
         Wu = put16(wk)
         slab_slots(Wu, n_u, C2p)
-        gu = sd[apfx + ".weight_conv.4.group_norm.weight"]
-        a.vecu = putf(vec3(n_u, lay_u, sd[apfx + ".weight_conv.2.bias"], gu, sd[apfx + ".weight_conv.4.group_norm.bias"])).data_ptr()
-        a.n_u, a.gsu, a.nnu, a.invu = n_u, lay_u[3], lay_u[2], 1.0 / (lay_u[4] * npx)
+        a.vecu = putf(vec3(n_u, lay_u, apfx + ".weight_conv.2", apfx + ".weight_conv.4.group_norm")).data_ptr()
+        a.n_u, a.gsu, a.nnu, a.invu = n_u, lay_u.gs, lay_u.n_norm, 1.0 / (lay_u.gs_logical * npx)
         fl += w2k.size
         # tail
         cout = body["cout"]
         vlay = gn_layout(cout)
         w5 = np.zeros((cout, n_u), np.float32)
-        w5[:, lay_u[0]] = self._w(apfx + ".weight_conv.5.weight")
+        w5[:, lay_u.index] = self._w(apfx + ".weight_conv.5.weight")
         wv = self._w(apfx + ".feat_out_conv.0.weight")
         W5, Wv = put16(w5), put16(wv)
         assert cout % trows == 0 or npx_log2 == 8
@@ -928,14 +1024,8 @@ class DenoiserEngine:
                 for kc in range(0, k // 32, cps):
                     slots.append((Wt.data_ptr() + 2 * ((kc * cout + cbk * trows) * 32), cout * 32, min(trows, cout - cbk * trows), 1,
                                   min(cps, k // 32 - kc)))
-        vect = np.zeros((4, cout), np.float32)
-        vect[0] = sd[apfx + ".weight_conv.5.bias"]
-        vect[1] = sd[apfx + ".feat_out_conv.0.bias"]
-        gam = sd[apfx + ".feat_out_conv.1.group_norm.weight"]
-        vect[2, :gam.shape[0]] = gam
-        vect[3, :gam.shape[0]] = sd[apfx + ".feat_out_conv.1.group_norm.bias"]
-        a.vect = putf(vect).data_ptr()
-        a.n_out, a.gsv, a.nnv, a.invv = cout, vlay[3], vlay[2], 1.0 / (vlay[4] * npx)
+        a.vect = putf(self._tail_vectors(apfx, cout)).data_ptr()
+        a.n_out, a.gsv, a.nnv, a.invv = cout, vlay.gs, vlay.n_norm, 1.0 / (vlay.gs_logical * npx)
         fl += self._w(apfx + ".weight_conv.5.weight").size + wv.size
         # tables and vectors
         ta, tb = ctx["ta"], ctx["tb"]
@@ -948,9 +1038,9 @@ class DenoiserEngine:
             assert ctx["rvv"].shape[1] == n_mo
         add0 = ctx["add1"]
         if add0 is not None:
-            a.add0 = add0[0].data_ptr() + 4 * add0[1]
-            a.add0_bs, a.add0_stride = add0[2], add0[4]
-            a.add0_idx = None if add0[3] is None else add0[3].data_ptr()
+            a.add0 = add0.vec.data_ptr() + 4 * add0.off
+            a.add0_bs, a.add0_stride = add0.bs, add0.idx_stride
+            a.add0_idx = _dp(add0.idx)
         a.sc = body["scale"].data_ptr() + 4 * body["C1p"]
         a.sh = body["shift"].data_ptr() + 4 * body["C1p"]
         a.aff_bs = body["ldT"]
@@ -971,6 +1061,18 @@ class DenoiserEngine:
             flops=2 * rows * fl, nbytes=(2 * B * 16 * ta.shape[1] * 2, B * 16 * cout * 2),
             name="block_body_kernel<%d, %s, %d, %d, %d>" % (npx_log2, "true" if rest else "false", (c2 // 32) if rest else 0,
                                                             n_mo // 32, n_u // 32))
+
+    def _tail_vectors(self, apfx, n):
+        """[scores bias | values bias | values gamma | values beta] of an attention tail, float rows [4][n]"""
+        sd = self.sd
+        cout = sd[apfx + ".weight_conv.5.weight"].shape[0]
+        gam = sd[apfx + ".feat_out_conv.1.group_norm.weight"]
+        vec = np.zeros((4, n), np.float32)
+        vec[0, :cout] = sd[apfx + ".weight_conv.5.bias"]
+        vec[1, :cout] = sd[apfx + ".feat_out_conv.0.bias"]
+        vec[2, :gam.shape[0]] = gam
+        vec[3, :gam.shape[0]] = sd[apfx + ".feat_out_conv.1.group_norm.bias"]
+        return vec
 
     def _attention(self, apfx, npx_log2, K, g, q_in, mo, mlp_first, mlp_res, out, out_ld_buf, gather=None, qctx=None,
                    extra_q=(), pair=None, body=None):
@@ -998,7 +1100,7 @@ class DenoiserEngine:
         Tq, ssum, ssq = qctx["Tq"], qctx["ssum"], qctx["ssq"]
         Tk = None if pair is not None else self._buf(rows, C2p, cm=True)
         kseg = dict(w=self._w(apfx + ".grouped_feat_conv.weight"), bias=sd[apfx + ".grouped_feat_conv.bias"],
-                    mode=EPI_STATS, flags=F_PRE_RELU, out=Tk, stats=(ssum, ssq, C1p, 1.0))
+                    mode=EPI_STATS, flags=F_PRE_RELU, out=Tk, stats=Stats(ssum, ssq, C1p, 1.0))
         # GroupNorm over the concatenation [q | k] (weight_conv.1): groups may straddle the two producers
         Ct = C1 + C2
         G = min(32, Ct)
@@ -1041,41 +1143,29 @@ class DenoiserEngine:
             ctx = self._pair_first(npx_log2, K, feat_tab, Cf, [mlp_first, mlp_res, kseg], coords,
                                    fin=fin_struct() if pair_fin else None,
                                    lead_segs=([qctx["qseg"]] + [e["qseg"] for e in extra_q]) if q_rides else ())
-            ctx.update(off1=ctx["offs"][0], offr=ctx["offs"][1], offk=ctx["offs"][2], lay1=mlp_first["layout"],
-                       add1=mlp_first.get("addvec"))
+            off1, offr, offk = ctx["offs"]
+            ctx.update(off1=off1, offr=offr, offk=offk, lay1=mlp_first["layout"], add1=_rec(AddVec, mlp_first.get("addvec")))
             rres = ru(mlp_res["w"].shape[0])
             ctx["rvv"] = None
             if K == 8:  # coefficient vectors of the two per-slot scalars for the res_connect channels (RAW segment: unscaled)
                 ctx["rvv"] = self.A.put(np.ascontiguousarray(ctx["vv_in"][:, ctx["offr"]:ctx["offr"] + rres]))
             self.pair_ctx = ctx
-        elif gather is not None and gather[3] * 32 >= int(os.environ.get("SLIDE_SPLIT_FIRST", "1000000")):
+        elif gather is not None and gather.chunks * 32 >= int(os.environ.get("SLIDE_SPLIT_FIRST", "1000000")):
             # (opt-in, SLIDE_SPLIT_FIRST=<min feature channels>: measured neutral to -1.5 % on the feature plan -- the
             # 256-row launch is bound by its epilogue, not by its K loop, and the per-point GEMM is one more launch)
             # The layer is linear in its input and the leading Cf input channels of row (point, neighbour) are the
             # NEIGHBOUR's feature row, the same for every query point: their products are evaluated once per point
             # (a 16-row GEMM over the feature table, 1/K of the MACs) and enter the per-neighbour GEMM -- now over the
             # coordinate channels only -- as a gathered pre-activation term.
-            tab, kidx, _, nsplit = gather
-            Cf = nsplit * 32
-            segs, ysegs, off = [], [], 0
-            for sg in (mlp_first, mlp_res, kseg):
-                lay = sg.get("layout")
-                Op = ru(sg["w"].shape[0] if lay is None else lay[1])
-                segs.append((sg, off))
-                off += Op
-            Y = self._buf(B * 16, off)
-            for sg, o_ in segs:
-                lay = sg.get("layout")
-                ysegs.append(dict(w=sg["w"][:, :Cf], mode=EPI_RAW, out=Y, out_coff=o_,
-                                  layout=None if lay is None else (lay[0], lay[1], 0, 1, 1)))
-            self._gemm(tab, 4, ysegs)
-            tails = []
-            for sg, o_ in segs:
-                t_ = dict(sg)
-                t_["w"] = sg["w"][:, Cf:]
-                t_["pre_add"] = (Y, -kshift, o_)
-                tails.append(t_)
-            self._gemm(g, npx_log2, tails, pre_gather=kidx)
+            Cf = gather.chunks * 32
+            segs = (mlp_first, mlp_res, kseg)
+            offs, ldy = seg_offsets(segs)
+            Y = self._buf(B * 16, ldy)
+            self._gemm(gather.table, 4, [dict(w=sg["w"][:, :Cf], mode=EPI_RAW, out=Y, out_coff=o_,
+                                              layout=None if sg.get("layout") is None else sg["layout"].raw())
+                                         for sg, o_ in zip(segs, offs)])
+            self._gemm(g, npx_log2, [dict(sg, w=sg["w"][:, Cf:], pre_add=PreAdd(Y, -kshift, o_)) for sg, o_ in zip(segs, offs)],
+                       pre_gather=gather.nbr)
         else:
             self._gemm(g, npx_log2, [mlp_first, mlp_res, kseg], gather=gather)
         self._sync(0, 1)  # the key statistics are ready
@@ -1086,7 +1176,7 @@ class DenoiserEngine:
             self._lane = 1
             d = fin_d
             # (only the small-launch kernel finalises: same grid bound as run_gemm's dispatch)
-            n_cob_p = ru(gn_layout(inter)[1]) // 32
+            n_cob_p = ru(gn_layout(inter).width) // 32
             fuse_fin = (self.prec == 1 and self.use_glds and os.environ.get("SLIDE_FUSE_FIN", "1") != "0" and
                         ((B * 16 + 63) // 64) * ((n_cob_p + 1) // 2) <= 1024)
             gn_fin = None
@@ -1101,40 +1191,39 @@ class DenoiserEngine:
             lay = gn_layout(inter)
             w2 = self._w(apfx + ".weight_conv.2.weight")
             # query half, once per point: P = W2[:, :C1] . GN(relu(q))      (no bias, raw)
-            P = self.A.zeros(B * 16, ru(lay[1]), dtype=self.adt)
-            self._gemm(Tq, 4, [dict(w=w2[:, :C1], mode=EPI_RAW, layout=(lay[0], lay[1], 0, 1, 1), out=P)],
-                       in_affine=(scale, shift, 0, ldT), gn_fin=gn_fin)
+            P = self.A.zeros(B * 16, ru(lay.width), dtype=self.adt)
+            self._gemm(Tq, 4, [dict(w=w2[:, :C1], mode=EPI_RAW, layout=lay.raw(), out=P)],
+                       in_affine=InAffine(scale, shift, 0, ldT), gn_fin=gn_fin)
             if body is not None:  # the block body kernel (SLIDE_OP_BLOCK_BODY) takes it from here
                 self._lane = 0
                 body.update(P=P, lay_u=lay, scale=scale, shift=shift, C1=C1, C1p=C1p, C2p=C2p, ldT=ldT, w2=w2, apfx=apfx,
                             cout=cout, inter=inter)
                 return ("body",)
             # neighbour half: u = GN4(relu(W2[:, C1:] . GN(relu(k)) + bias + P[point]))
-            u = self._buf(rows, ru(lay[1]), cm=True, fm=self._is_fm(mo))
+            u = self._buf(rows, ru(lay.width), cm=True, fm=self._is_fm(mo))
             useg = dict(w=w2[:, C1:], bias=sd[apfx + ".weight_conv.2.bias"], mode=EPI_NORM,
-                        flags=F_PRE_RELU, layout=lay, out=u, pre_add=(P, kshift),
+                        flags=F_PRE_RELU, layout=lay, out=u, pre_add=PreAdd(P, kshift),
                         gn=(sd[apfx + ".weight_conv.4.group_norm.weight"], sd[apfx + ".weight_conv.4.group_norm.bias"]))
             if pair is not None:  # the keys max(a[q] + b[p], 0) * scale + shift are generated from the pair tables
                 ctx = self.pair_ctx
-                self._gemm(None, npx_log2, [useg], in_affine=(scale, shift, C1p, ldT),
+                self._gemm(None, npx_log2, [useg], in_affine=InAffine(scale, shift, C1p, ldT),
                            gx=dict(ta=ctx["ta"], tb=ctx["tb"], coff=ctx["offk"], k_pad=C2p, rows=rows, mode=1, vv=ctx["vv"]),
                            pair_tabs=ctx["tabs"])
             else:
-                self._gemm(Tk, npx_log2, [useg], in_affine=(scale, shift, C1p, ldT))
+                self._gemm(Tk, npx_log2, [useg], in_affine=InAffine(scale, shift, C1p, ldT))
             vlay = gn_layout(cout)
-            if (self.prec == 1 and self.use_glds and os.environ.get("SLIDE_ATTN_TAIL", "1") != "0" and
-                    np.array_equal(vlay[0], np.arange(cout))):
+            if (self.prec == 1 and self.use_glds and os.environ.get("SLIDE_ATTN_TAIL", "1") != "0" and vlay.unpermuted):
                 self._lane = 0
                 return ("fused", u, lay)  # scores are computed inside the fused attention tail (finish)
             # round 5: the same tail in the split arithmetic on float rows (csrc/gemm_gxs.hip attn_tail_split_kernel;
             # SLIDE_TAIL_SPLIT=0: scores GEMM + values GEMM + combine launch).  Its single-accumulator split needs |w| < 32.
-            if (self.use_gxs and os.environ.get("SLIDE_TAIL_SPLIT", "1") != "0" and np.array_equal(vlay[0], np.arange(cout))
+            if (self.use_gxs and os.environ.get("SLIDE_TAIL_SPLIT", "1") != "0" and vlay.unpermuted
                     and self._split1_ok(self._w(apfx + ".weight_conv.5.weight"), self._w(apfx + ".feat_out_conv.0.weight"))):
                 self._lane = 0
                 return ("fused", u, lay)
             S = self._buf(rows, cout)
             self._gemm(u, npx_log2, [dict(w=self._w(apfx + ".weight_conv.5.weight"), bias=sd[apfx + ".weight_conv.5.bias"],
-                                          mode=EPI_RAW, out=S)], in_cols=lay[0])
+                                          mode=EPI_RAW, out=S)], in_cols=lay.index)
             self._lane = 0
             return S
 
@@ -1144,19 +1233,13 @@ class DenoiserEngine:
                 vlay = gn_layout(cout)
                 Cp = ru(cout)
                 w5 = np.zeros((Cp, u.shape[1]), np.float32)
-                w5[np.ix_(np.arange(cout), lay[0])] = self._w(apfx + ".weight_conv.5.weight")
+                w5[np.ix_(np.arange(cout), lay.index)] = self._w(apfx + ".weight_conv.5.weight")
                 wv_l = self._w(apfx + ".feat_out_conv.0.weight")
                 wv = np.zeros((Cp, mo.shape[1]), np.float32)
                 wv[:cout, :wv_l.shape[1]] = wv_l
-                vec = np.zeros((4, Cp), np.float32)
-                vec[0, :cout] = sd[apfx + ".weight_conv.5.bias"]
-                vec[1, :cout] = sd[apfx + ".feat_out_conv.0.bias"]
-                gam = sd[apfx + ".feat_out_conv.1.group_norm.weight"]
-                vec[2, :gam.shape[0]] = gam
-                vec[3, :gam.shape[0]] = sd[apfx + ".feat_out_conv.1.group_norm.bias"]
-                cmw = (lambda w: np.ascontiguousarray(w.reshape(w.shape[0], -1, 32).transpose(1, 0, 2))) if self.use_cm else (lambda w: w)
+                cmw = chunk_major if self.use_cm else (lambda w: w)
                 wdt = torch.float16 if self.prec == 1 else torch.float32  # (split tail: float row-major weights)
-                d = [self.A.put(cmw(w5), wdt), self.A.put(cmw(wv), wdt), self.A.put(vec)]
+                d = [self.A.put(cmw(w5), wdt), self.A.put(cmw(wv), wdt), self.A.put(self._tail_vectors(apfx, Cp))]
                 assert out.dtype == self.adt and u.dtype == self.adt and mo.dtype == self.adt and not self._is_cm(out)
                 assert self._is_fm(u) == self._is_fm(mo)
                 self._sync(1, 0)
@@ -1165,24 +1248,21 @@ class DenoiserEngine:
                 if self.use_cm and os.environ.get("SLIDE_CM_TABLES", "0") != "0" and npx_log2 == 8:  # (SA outputs feed gathers)
                     out_cm = self._cm_copy[out.data_ptr()] = self.A.zeros(out.shape[0], out.shape[1], dtype=self.adt)
                 self._tail_of[out.data_ptr()] = self._emit(make_op(OP_ATTN_TAIL, i=(rows, self._ldp(u), u.shape[1], self._ldp(mo), mo.shape[1], Cp // 32, npx_log2,
-                                                    vlay[3], vlay[2], out.shape[1]),
+                                                    vlay.gs, vlay.n_norm, out.shape[1]),
                                         # f[1]: 1 = chunk-major operands, + 2 = two-stage ring at three workgroups per CU (opt-in,
                                         # SLIDE_TAIL_OCC3=1: measured neutral, 373.0 vs 372.3 shapes/s)
-                                        f=(1.0 / (vlay[4] * npx), (1.0 if self.use_cm else 0.0) + (8.0 if self.prec != 1 else 0.0) +
+                                        f=(1.0 / (vlay.gs_logical * npx), (1.0 if self.use_cm else 0.0) + (8.0 if self.prec != 1 else 0.0) +
                                            (2.0 if os.environ.get("SLIDE_TAIL_OCC3", "0") != "0" else 0.0) +
                                            (4.0 if (Cp // 32) % 4 == 0 and Cp // 32 >= int(os.environ.get("SLIDE_TAIL_WIDE", "1000")) else 0.0) +
                                            (16.0 if self._is_fm(mo) else 0.0)),  # bit 4: u / mo fragment-major
                                         p=(u.data_ptr(), d[0].data_ptr(), mo.data_ptr(), d[1].data_ptr(), out.data_ptr(),
                                            d[2].data_ptr(), _dp(out_cm))),
-                    flops=2 * rows * cout * (len(lay[0]) + wv_l.shape[1]),  # logical channels
+                    flops=2 * rows * cout * (len(lay.index) + wv_l.shape[1]),  # logical channels
                     name=None if self.prec == 1 else "attn_tail_split_kernel<%d>" % npx_log2)
                 return
             # lane 0 (value branch), then the join
             V = self._buf(rows, cout)
-            self._gemm(mo, npx_log2, [dict(w=self._w(apfx + ".feat_out_conv.0.weight"), bias=sd[apfx + ".feat_out_conv.0.bias"],
-                                           mode=EPI_NORM, flags=F_POST_RELU, layout=gn_layout(cout), out=V,
-                                           gn=(sd[apfx + ".feat_out_conv.1.group_norm.weight"],
-                                               sd[apfx + ".feat_out_conv.1.group_norm.bias"]))])
+            self._gemm(mo, npx_log2, [self._conv_gn_relu(apfx + ".feat_out_conv.0", apfx + ".feat_out_conv.1.group_norm", out=V)])
             assert out.dtype == self.adt
             self._sync(1, 0)
             self._emit(make_op(OP_ATTN_COMBINE, i=(rows // K, cout, S.shape[1], V.shape[1], out.shape[1], K, self.prec),
@@ -1207,7 +1287,7 @@ class DenoiserEngine:
         # only coordinate channels left: loop-invariant when the coordinates are a fixed condition
         self._emit(make_op(kind, i=(B, C, feat_in.shape[1], ldg, K, self.prec, c_begin, ldg - c_begin), p=ptrs + (g.data_ptr(),)),
                    role="xyz_copy" if nsplit and c_begin == C else None)
-        return g, ((feat_in, self.kidx, K, nsplit) if nsplit else None), rows
+        return g, (Gather(feat_in, self.kidx, K, nsplit) if nsplit else None), rows
 
     def _sa_module(self, i, feat_in, C, extra_q=()):
         sd, B = self.sd, self.B
@@ -1323,12 +1403,12 @@ class DenoiserEngine:
         if fr is None or self.prec != 1 or os.environ.get("SLIDE_POINT_CHAIN", "1") == "0":
             return None
         m2 = fr["m2"]
-        ident = lambda c: (lambda l: np.array_equal(l[0], np.arange(c)) and l[1] == c and l[2] == c and l[3] == 4)(gn_layout(c))
+        ident = lambda c: gn_layout(c).identity and gn_layout(c).gs == 4
         c2 = sd[m2 + ".second_mlp.0.weight"].shape[0]
         has_t, has_c = (m2 + ".fc.weight") in sd, (m2 + ".fc_condition.weight") in sd
         if not (fr["n1"] == 128 and fr["n2"] == 128 and c2 == 128 and (m2 + ".rest_mlp.0.weight") not in sd and ident(128)
                 and len(fr["launches"]) == 2 and self.plan[-4:] == fr["launches"] + head and fr["Z"].shape[1] <= 192 and w0.shape[0] == 128
-                and np.array_equal(lay0[0], np.arange(128)) and lay0[3] == 4 and lay0[2] == 128 and 128 < dec0.shape[1] <= 160
+                and lay0.identity and lay0.gs == 4 and 128 < dec0.shape[1] <= 160
                 and w1.shape[1] == 128 and self.out_dim <= 64 and sd["fc_lyaer.1.weight"].shape[0] == 128):
             return None
         A = self.A
@@ -1338,13 +1418,13 @@ class DenoiserEngine:
         Wz[128:, :zin] = self._w(m2 + ".res_connect.weight")
         vz = np.stack([sd[m2 + ".first_mlp.0.bias"], sd[m2 + ".first_mlp.1.group_norm.weight"], sd[m2 + ".first_mlp.1.group_norm.bias"],
                        sd[m2 + ".res_connect.bias"]]).astype(np.float32)
-        v2 = np.stack([sd[m2 + ".second_mlp.0.bias"], sd[m2 + ".second_mlp.1.group_norm.weight"],
-                       sd[m2 + ".second_mlp.1.group_norm.bias"]]).astype(np.float32)
+        v2 = epi_vectors(lay0, 128, sd[m2 + ".second_mlp.0.bias"], (sd[m2 + ".second_mlp.1.group_norm.weight"],
+                                                                    sd[m2 + ".second_mlp.1.group_norm.bias"]))
         n1c = ru(self.out_dim) // 32
         W0 = np.zeros((128, dec0.shape[1]), np.float32); W0[:, :w0.shape[1]] = w0
         W1 = np.zeros((n1c * 32, 128), np.float32); W1[:w1.shape[0]] = w1
         b1 = np.zeros(n1c * 32, np.float32); b1[:w1.shape[0]] = sd["fc_lyaer.3.bias"]
-        v0 = np.stack([sd["fc_lyaer.0.bias"], sd["fc_lyaer.1.weight"], sd["fc_lyaer.1.bias"]]).astype(np.float32)
+        v0 = epi_vectors(lay0, 128, sd["fc_lyaer.0.bias"], (sd["fc_lyaer.1.weight"], sd["fc_lyaer.1.bias"]))
         off = lambda lst, pfx: sum(w for _, w in lst[:[p_ for p_, _ in lst].index(pfx)])
         W2 = self._w(m2 + ".second_mlp.0.weight")
         for role, e in zip(("pc0", "pc1", "pc2", "pc3"), self.plan[-4:]):
@@ -1463,22 +1543,20 @@ class DenoiserEngine:
         hh = self._buf(B * 16, sd["fc_lyaer.0.weight"].shape[0])
         assert sd["fc_lyaer.0.weight"].shape[1] == c + 3
         head = [None, None]
-        head[0] = self._gemm(dec0, 4, [dict(w=self._w("fc_lyaer.0.weight"), bias=sd["fc_lyaer.0.bias"], mode=EPI_NORM,
-                                  flags=F_POST_RELU, layout=gn_layout(sd["fc_lyaer.0.weight"].shape[0]), out=hh,
-                                  gn=(sd["fc_lyaer.1.weight"], sd["fc_lyaer.1.bias"]))])
+        head[0] = self._gemm(dec0, 4, [self._conv_gn_relu("fc_lyaer.0", "fc_lyaer.1", out=hh)])
         self.eps_pad = self._buf(B * 16, self.out_dim, dtype=torch.float32)
         head[1] = self._gemm(hh, 4, [dict(w=self._w("fc_lyaer.3.weight"), bias=sd["fc_lyaer.3.bias"], mode=EPI_RAW, out=self.eps_pad)])
         # what SLIDE_OP_HEAD_UPDATE needs (the samplers replace the two head GEMMs + their update launch by it, diffusion.py)
         self.head = None
         w0, w1 = self._w("fc_lyaer.0.weight"), self._w("fc_lyaer.3.weight")
         lay0 = gn_layout(w0.shape[0])
-        if (self.prec == 1 and w0.shape[0] == 128 and np.array_equal(lay0[0], np.arange(128)) and lay0[3] == 4 and lay0[2] == 128
+        if (self.prec == 1 and w0.shape[0] == 128 and lay0.identity and lay0.gs == 4
                 and dec0.shape[1] <= 160 and w1.shape[1] == 128 and self.out_dim <= 64 and sd["fc_lyaer.1.weight"].shape[0] == 128):
             W0 = np.zeros((128, dec0.shape[1]), np.float32); W0[:, :w0.shape[1]] = w0
             n1c = ru(self.out_dim) // 32
             W1 = np.zeros((n1c * 32, 128), np.float32); W1[:w1.shape[0]] = w1
             b1 = np.zeros(n1c * 32, np.float32); b1[:w1.shape[0]] = sd["fc_lyaer.3.bias"]
-            v0 = np.stack([sd["fc_lyaer.0.bias"], sd["fc_lyaer.1.weight"], sd["fc_lyaer.1.bias"]]).astype(np.float32)
+            v0 = epi_vectors(lay0, 128, sd["fc_lyaer.0.bias"], (sd["fc_lyaer.1.weight"], sd["fc_lyaer.1.bias"]))
             head[0].roles.add("head0"); head[1].roles.add("head1")
             self.head = dict(X=dec0, k0=dec0.shape[1], n1c=n1c,
                              W0=self.A.put(W0, torch.float16), W1=self.A.put(W1, torch.float16), v0=self.A.put(v0), b1=self.A.put(b1))
