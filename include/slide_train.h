@@ -44,6 +44,16 @@ SLIDE_API int slide_gn_rows_bwd(int B, int S, int ld, int G, int n_norm, int fla
  * rows >= 128 with scratch NULL. */
 SLIDE_API int slide_col_sums(long long rows, int ld, const float *x, float *out, float *scratch, slide_stream_t stream);
 
+/* out [B][ld] = the column sums of each sample's S rows of x [B*S][ld]: out[b][c] = sum_s x[(b, s)][c] (the gradient of a
+ * per-sample vector added to every row of its sample -- the class- / t-embedding term of an Mlp); out is written in full.
+ * Coalesced float4 row reads, no atomics, and a fixed order of additions that depends on S and ld only: a sample's sums do not
+ * depend on B or on its position in the batch, and two runs are bit-equal.  S < 128: one launch, one workgroup per sample, scratch
+ * unused (may be NULL).  S >= 128: two launches, n = min(256, S / 64) row chunks per sample into scratch (B * n * ld floats; never
+ * more than B * 256 * ld), then the same kernel over each sample's partial rows.  gridDim.y = B: B <= 65535.  B = 0: 0 without a
+ * launch, nothing read or written; S = 0 with B > 0: out zero-filled (a memset), no launch.  -3, nothing written: ld not a positive
+ * multiple of 32 up to 1024, B < 0 or > 65535, S < 0, out NULL, x NULL with S > 0, or S >= 128 with scratch NULL. */
+SLIDE_API int slide_col_sums_seg(int B, long long S, int ld, const float *x, float *out, float *scratch, slide_stream_t stream);
+
 /* grouped rows out[(b,p,k)][0..C) = feat[b][idx[b][p][k]][0..C): dfeat [B*N][ldf] += dout [B*np*K][ldg] (atomic; dfeat must be
  * zero-initialised); counts (B*np) int32 or NULL: centres with count 0 carried zero features and receive nothing.  Only the
  * elements that a gradient row lands on are touched: channels >= C and rows that no live centre indexes keep their value. */

@@ -195,6 +195,7 @@ PROTOTYPES = {name: _proto(args) for name, args in {
     # include/slide_train.h
     "slide_gn_rows_bwd": "iiiiiipppppppppp",
     "slide_col_sums": "qipppp",
+    "slide_col_sums_seg": "iqipppp",
     "slide_group_rows_bwd": "iiiiiiippppp",
     "slide_group_rows_coord_bwd": "iiiiiiippppppppp",
     "slide_concat_qk_bwd": "qiiiiiippppp",

@@ -215,6 +215,37 @@ __global__ __launch_bounds__(256) void col_sums_kernel(long long rows, int ld, i
   }
 }
 
+// ---------------------------------------------------------------------------------------------------- per-sample column sums
+// part[(b, chunk)][c] = sum over the chunk's rows of sample b of x[(b, s)][c] (the gradient of a per-sample vector added to every
+// row of its sample: x[(b, s)] += vec[b]).  col_sums_kernel's layout at full width: ld / 4 threads per row, rt = 256 / (ld / 4)
+// rows in flight, every access a coalesced float4 of a row; a thread adds its rows in ascending order, then one thread per column
+// adds the rt lane sums in ascending lane.  Workgroup (chunk, b) of a (nchunk, B) grid; the second pass is the same kernel over
+// the nchunk partial rows of each sample (S = rpc = nchunk, one chunk).  The order of the additions depends on S and ld only.
+__global__ __launch_bounds__(256) void col_sums_seg_kernel(long long S, int ld, long long rpc, const float *__restrict__ x,
+                                                           float *__restrict__ part) {
+  __shared__ float red[256 * 4];
+  const int cn = ld / 4, rt = 256 / cn;
+  const int pr = threadIdx.x / cn, pc = threadIdx.x - pr * cn;
+  const long long r0 = (long long)blockIdx.x * rpc, r1 = min(S, r0 + rpc);
+  if (pr < rt) {
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    const float *xs = x + ((size_t)blockIdx.y * (size_t)S) * ld + pc * 4;
+    for (long long r = r0 + pr; r < r1; r += rt) {
+      const float4 v = *reinterpret_cast<const float4 *>(xs + (size_t)r * ld);
+      s[0] += v.x; s[1] += v.y; s[2] += v.z; s[3] += v.w;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) red[pr * ld + pc * 4 + j] = s[j];
+  }
+  __syncthreads();
+  float *po = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * ld;
+  for (int c = threadIdx.x; c < ld; c += 256) {
+    float a = 0.f;
+    for (int r = 0; r < rt; ++r) a += red[r * ld + c];
+    po[c] = a;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------- grouping (features)
 // forward: out[(b, p, k)][c] = feat[b][idx[b][p][k]][c] for c < C (a centre with an empty ball: zero features);
 // backward: dfeat[b][idx][c] += dout[row][c].  One thread per (row, 4 channels); fp32 atomics (the reference's backward does the same).
@@ -341,6 +372,26 @@ int slide_col_sums(long long rows, int ld, const float *x, float *out, float *sc
   if (!scratch) return -3;
   hipLaunchKernelGGL(col_sums_kernel, dim3((unsigned)nchunk), dim3(256), 0, (hipStream_t)stream, rows, ld, ld, rpc, x, scratch);
   hipLaunchKernelGGL(col_sums_kernel, dim3(1, ld / 32), dim3(256), 0, (hipStream_t)stream, nchunk, ld, 32, (int)nchunk, scratch, out);
+  return LAUNCH_STATUS();
+}
+
+int slide_col_sums_seg(int B, long long S, int ld, const float *x, float *out, float *scratch, slide_stream_t stream) {
+  if (ld <= 0 || ld % 32 || ld > 1024 || B < 0 || B > 65535 || S < 0) return -3;
+  if (B == 0) return 0;
+  if (!out) return -3;
+  if (S == 0) return (int)hipMemsetAsync(out, 0, (size_t)B * ld * sizeof(float), (hipStream_t)stream);
+  if (!x) return -3;
+  long long nchunk = S / 64;
+  nchunk = nchunk < 1 ? 1 : nchunk > 256 ? 256 : nchunk;
+  const long long rpc = (S + nchunk - 1) / nchunk;
+  nchunk = (S + rpc - 1) / rpc;
+  if (nchunk == 1) {
+    hipLaunchKernelGGL(col_sums_seg_kernel, dim3(1, B), dim3(256), 0, (hipStream_t)stream, S, ld, rpc, x, out);
+    return LAUNCH_STATUS();
+  }
+  if (!scratch) return -3;
+  hipLaunchKernelGGL(col_sums_seg_kernel, dim3((unsigned)nchunk, B), dim3(256), 0, (hipStream_t)stream, S, ld, rpc, x, scratch);
+  hipLaunchKernelGGL(col_sums_seg_kernel, dim3(1, B), dim3(256), 0, (hipStream_t)stream, nchunk, ld, nchunk, scratch, out);
   return LAUNCH_STATUS();
 }
 

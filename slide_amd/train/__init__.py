@@ -10,6 +10,11 @@ grouping.py   query_and_group_rows / group_knn_rows: QueryAndGroup and group_knn
 losses.py     util.training_loss (pointnet2/util.py:262-300) and LatentDiffusion.train_loss
               (pointnet2/diffusion_utils/diffusion.py:319-341); calc_cd_loss and autoencoder_losses, the differentiable calc_cd and the
               autoencoder's loss loop (pointnet2/models/autoencoder.py:60-87) on given decoder levels
+cloudnet.py   TrainableCloudNet: PointNet2CloudCondition of the decoder-level configs for any input size (FPS levels, cross-level
+              kNN feature propagation), on the same layers; add_vec_rows (functions.py) carries the class embedding, its backward is
+              slide_col_sums_seg
+decoder.py    TrainableDecoderLevel / TrainableDecoder: the decode side of the autoencoder with the reference's state-dict names;
+              losses.decoder_training_loss puts autoencoder_losses on its levels
 dp.py         data-parallel gradient averaging: bucketed all-reduce over torch.distributed (RCCL over xGMI; gloo in the CPU tests),
               the counterpart of pointnet2/distributed.py:99-151
 There is no CPU fallback: every Function launches kernels of libslide_hip.so."""

@@ -108,6 +108,39 @@ def col_sums(x):
     return buf[0]
 
 
+def col_sums_seg(x, B, S):
+    """per-sample column sums of x [B * S, ld] -> [B, ld] (csrc/train_ops.hip col_sums_seg_kernel, include/slide_train.h
+    slide_col_sums_seg): the reduction col_sums does over all rows, over the S rows of each sample -- torch's x.view(B, S, ld).sum(1)
+    is the reduction shape col_sums' docstring rules out on the training path"""
+    _chk(x)
+    ld = x.shape[1]
+    assert x.shape[0] == B * S
+    out = torch.empty(B, ld, device=x.device, dtype=torch.float32)
+    scratch = torch.empty(B * min(256, S // 64) * ld, device=x.device, dtype=torch.float32) if S >= 128 else None
+    check(lib().slide_col_sums_seg(B, S, ld, ptr(x), ptr(out), ptr(scratch), stream_of()), "slide_col_sums_seg")
+    return out
+
+
+class AddVecRows(torch.autograd.Function):
+    """x[(b, s)][c] += vec[b][c] on rows [B * S, ld], vec [B, C <= ld] (the class- / t-embedding term of Mlp_plus_t_emb,
+    pointnet2_modules.py:150-166).  The forward is an elementwise broadcast add (torch); the backward's dvec is the per-sample
+    column sum of dy over the S rows of a sample: slide_col_sums_seg."""
+
+    @staticmethod
+    def forward(ctx, x, vec, B, S):
+        _chk(x)
+        assert x.shape[0] == B * S and vec.shape[0] == B and vec.shape[1] <= x.shape[1], (x.shape, vec.shape, B, S)
+        ctx.cfg = (B, S, vec.shape[1])
+        return (x.view(B, S, -1) + pad_cols(vec, x.shape[1])[:, None, :]).reshape(B * S, -1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        B, S, C = ctx.cfg
+        dvec = col_sums_seg(dy.contiguous(), B, S)[:, :C] if ctx.needs_input_grad[1] else None
+        return dy if ctx.needs_input_grad[0] else None, dvec, None, None
+
+
 def _weight_grad(dy, x):
     """dW (padded) [op_, kp] = dy^T x over the rows: a library GEMM (hipBLASLt through torch) whose contraction is the LONG dimension
     (up to 65536 rows against 32..512 outputs), so it is split into row slabs -- a batched GEMM that fills the chip -- and the
@@ -371,6 +404,10 @@ def gn_rows(x, gamma, beta, B, S, G, pre_relu=False, post_relu=False):
 
 def group_rows(feat, xyz, new_xyz, idx, d2, flags, C, counts=None):
     return GroupRows.apply(feat, xyz, new_xyz, idx, d2, flags, C, counts)
+
+
+def add_vec_rows(x, vec, B, S):
+    return AddVecRows.apply(x, vec, B, S)
 
 
 def concat_qk(q, k, K, C1, C2):

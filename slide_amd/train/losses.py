@@ -1,7 +1,7 @@
 """Training losses of the two latent DDPMs, restated from the reference (forward = slide_amd.train.denoiser.TrainableDenoiser or any
 callable net(x_t, ts, label) -> eps prediction).  Random timesteps and noise are drawn here unless they are passed in (the parity
 tests inject the reference's); and the autoencoder's Chamfer losses (calc_cd_loss, autoencoder_losses) on the differentiable
-Chamfer sums of functions.ChamferCD."""
+Chamfer sums of functions.ChamferCD, with the decode side's training loss on top (decoder_training_loss)."""
 import numpy as np
 import torch
 
@@ -124,3 +124,17 @@ def autoencoder_losses(l_xyz_decoder, pointcloud, feature_weight, loss_type='cd_
         loss_dict['training_loss'] = loss
         loss_list.append(loss_dict)
     return loss_list
+
+
+def decoder_training_loss(decoder, keypoint, feature_at_keypoint, label, pointcloud, feature_weight, loss_type='cd_p', fps_start_idx=None):
+    """the training loss of the decode side (slide_amd.train.decoder.TrainableDecoder): l_xyz_decoder = decoder.decode(keypoint,
+    feature_at_keypoint, label), loss_list = autoencoder_losses on its levels against `pointcloud`, loss = the sum over the levels of
+    training_loss.mean() (pointnet2/train_autoencoder.py:179-181).  -> (loss, loss_list); gradients reach every decode-side parameter,
+    the latent features and the key points.  Capturable: GraphedTrainingStep(decoder, optimizer, lambda: decoder_training_loss(...)[0])
+    with a fixed fps_start_idx tensor or None (drawn on the device)."""
+    l_xyz_decoder = decoder.decode(keypoint, feature_at_keypoint, label, fps_start_idx=fps_start_idx)
+    loss_list = autoencoder_losses(l_xyz_decoder, pointcloud, feature_weight, loss_type=loss_type, fps_start_idx=fps_start_idx)
+    loss = loss_list[0]['training_loss'].mean()
+    for d in loss_list[1:]:
+        loss = loss + d['training_loss'].mean()
+    return loss, loss_list
