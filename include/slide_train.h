@@ -107,6 +107,41 @@ SLIDE_API int slide_chamfer_cd_bwd(int b, int n1, int n2, int f, const float *x,
                                    const int64_t *i1, const float *d2, const int64_t *i2, const float *dred, float *dx, float *dy,
                                    slide_stream_t stream);
 
+/* The ENCODE side of autoencoder training (csrc/encoder_ops.hip).  Reference: the maxima of Pnet2Stage, pointnet2/models/pnet.py:32-40,
+ * and DiagonalGaussianDistribution, pointnet2/data_utils/distributions.py:4-43, as pointnet2/models/point_upsample_decoder.py:96-147
+ * applies it.  Common to the four: -3 with nothing written for a leading dimension that is not a positive multiple of 32 up to 1024,
+ * B < 0, S < 0, S = 0 with B > 0, or a NULL among the pointers not marked optional; B = 0: 0 without a launch.  Inputs are finite;
+ * NaN handling is not specified. */
+
+/* out [B][ld], arg [B][ld] (int32): out[b][c] = max_s x[(b, s)][c] over the S >= 1 rows of sample b for c < C, arg[b][c] = the LOWEST
+ * s that attains it (the first maximum in scan order: what max_pool2d's backward routes to).  Columns C..ld: out = 0, arg = -1.  One
+ * workgroup per sample; a sample's result does not depend on B or on its position in the batch.  -3 also for C outside 0..ld. */
+SLIDE_API int slide_col_max_seg(int B, int S, int C, int ld, const float *x, float *out, int *arg, slide_stream_t stream);
+
+/* dx [B*S][ld], written in full: dx[(b, s)][c] = dy[b][c] where arg[b][c] == s, else 0 (arg = -1 in the pad columns: zeros).  A
+ * gather: every element is stored once by the thread that owns it; no atomics, no zero fill. */
+SLIDE_API int slide_col_max_seg_bwd(int B, int S, int ld, const int *arg, const float *dy, float *dx, slide_stream_t stream);
+
+/* params [B*S][ldp]: mean in columns [0, C), log-variance in [C, 2C) (torch.chunk(parameters, 2, dim=1) of the reference's
+ * channel-first tensor), 1 <= C, 2C <= ldp, C <= ldz.  lv = min(max(logvar, -30), 20).
+ *   z [B*S][ldz]:  z[(b, s)][c] = mean + exp(0.5 lv) * eps[(b, s)][c] for c < C, 0 in columns C..ldz; eps [B*S][ldz], OPTIONAL:
+ *                  NULL gives z = mean (the posterior's mode).  The kernel draws no numbers.
+ *   kl [B], OPTIONAL (NULL: not computed):  kl[b] = 0.5 * sum over the sample's S x C elements of (mean^2 + exp(lv) - 1 - lv).
+ * One workgroup of 256 threads per sample: thread t adds the terms of the elements t, t + 256, ... of the sample's S x ldz block in
+ * ascending order, the 256 partial sums go through a fixed tree (a wave's xor butterfly 32, 16, .., 1, then the four wave sums in
+ * ascending wave).  The order depends on S, C and ldz only: kl[b] is bit-equal over runs, over B and over the sample's position in
+ * the batch.  exp is expf (1 ulp).  -3 also for S * ldz >= 2^31. */
+SLIDE_API int slide_gauss_posterior_fwd(int B, int S, int C, int ldp, int ldz, const float *params, const float *eps, float *z,
+                                        float *kl, slide_stream_t stream);
+
+/* dparams [B*S][ldp], written in full (columns 2C..ldp zero), everything recomputed from params; dz [B*S][ldz] and dkl [B] are each
+ * OPTIONAL (NULL: that term is 0), eps as in the forward (NULL: the dz term of dlogvar is 0):
+ *   dmean   = dz + dkl[b] * mean
+ *   dlogvar = m * (dz * eps * 0.5 * exp(0.5 lv) + dkl[b] * 0.5 * (exp(lv) - 1)),  m = 1 where -30 <= logvar <= 20, else 0
+ * (torch.clamp's backward: the gradient passes AT both bounds). */
+SLIDE_API int slide_gauss_posterior_bwd(int B, int S, int C, int ldp, int ldz, const float *params, const float *eps, const float *dz,
+                                        const float *dkl, float *dparams, slide_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

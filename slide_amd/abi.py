@@ -201,6 +201,10 @@ PROTOTYPES = {name: _proto(args) for name, args in {
     "slide_concat_qk_bwd": "qiiiiiippppp",
     "slide_attn_rows_bwd": "qiiiiippppppp",
     "slide_chamfer_cd_bwd": "iiiipipipppppppp",
+    "slide_col_max_seg": "iiiipppp",
+    "slide_col_max_seg_bwd": "iiipppp",
+    "slide_gauss_posterior_fwd": "iiiiippppp",
+    "slide_gauss_posterior_bwd": "iiiiipppppp",
     # include/experiments/slide_resident.h
     "slide_resident_run": "pp",
     "slide_sizeof_rop": "",

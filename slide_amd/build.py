@@ -26,7 +26,7 @@ SOURCES = [("point_ops.hip", ["-ffp-contract=off"]), ("chamfer.hip", ["-ffp-cont
            ("chamfer_pairwise.hip", ["-ffp-contract=off"]), ("chamfer_bwd.hip", ["-ffp-contract=off"]),
            ("occupancy_grid.hip", ["-ffp-contract=off"]), ("emd_pairwise.hip", ["-ffp-contract=off"]), ("engine.hip", UNROLL), ("gemm_ring.hip", UNROLL), ("attn_tail.hip", UNROLL),
            ("gemm_gx.hip", UNROLL), ("gemm_gxs.hip", UNROLL),
-           ("point_chain.hip", UNROLL), ("rows_ops.hip", []), ("train_ops.hip", []),
+           ("point_chain.hip", UNROLL), ("rows_ops.hip", []), ("train_ops.hip", []), ("encoder_ops.hip", []),
            ("group_coord_bwd.hip", ["-ffp-contract=off"]), ("lane_reduce_selftest.hip", [])]
 SOURCES_EXP = SOURCES + [("experiments/block_body.hip", UNROLL), ("experiments/gemm_xs.hip", UNROLL), ("experiments/gemm_chain.hip", UNROLL),
                          ("experiments/resident.hip", UNROLL)]

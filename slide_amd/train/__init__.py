@@ -15,6 +15,9 @@ cloudnet.py   TrainableCloudNet: PointNet2CloudCondition of the decoder-level co
               slide_col_sums_seg
 decoder.py    TrainableDecoderLevel / TrainableDecoder: the decode side of the autoencoder with the reference's state-dict names;
               losses.decoder_training_loss puts autoencoder_losses on its levels
+encoder.py    TrainableEncoder (PointNet2Encoder), TrainablePnet2Stage, TrainableKeypointEncoder (the key-point level: extractor, feature
+              mapper, the two KL posteriors) and TrainableAutoencoder; functions.col_max_seg / gauss_posterior on csrc/encoder_ops.hip;
+              losses.autoencoder_training_loss is the reference's forward plus its loss
 dp.py         data-parallel gradient averaging: bucketed all-reduce over torch.distributed (RCCL over xGMI; gloo in the CPU tests),
               the counterpart of pointnet2/distributed.py:99-151
 There is no CPU fallback: every Function launches kernels of libslide_hip.so."""

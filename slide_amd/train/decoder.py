@@ -13,7 +13,7 @@ TrainableDecoder = the key-point level's splitting head (`keypoint_encoder.fc_la
 decode_only=True) + the KeypointDecoder levels (`decoder.decoders.{i}.*`).  State-dict names are the reference's: the decode-side keys
 of a PointAutoencoder checkpoint load with load_state_dict(..., strict=True) after filtering, and a state dict saved here loads into
 the module path's PointAutoencoder(None, decoder_config_list).  The encoder, the key-point level's propagate_feature and its KL
-posterior are not built."""
+posteriors are encoder.py, whose TrainableAutoencoder builds on this class."""
 import numpy as np
 import torch
 import torch.nn as nn

@@ -394,6 +394,80 @@ def chamfer_cd(output, gt, f1_threshold=1e-4):
     return ChamferCD.apply(output, gt, float(f1_threshold))
 
 
+class ColMaxSeg(torch.autograd.Function):
+    """max over the S rows of each sample of x [B * S, ld] -> [B, ld] (columns >= C zero): the point-wise maxima of Pnet2Stage
+    (pointnet2/models/pnet.py:32-40).  One launch forward (slide_col_max_seg: the value and the first row that attains it), one
+    backward (slide_col_max_seg_bwd: a gather that writes dx in full) -- torch composes amax + argmax + a zero fill + a scatter."""
+
+    @staticmethod
+    def forward(ctx, x, B, S, C):
+        _chk(x)
+        assert x.shape[0] == B * S and 0 <= C <= x.shape[1], (x.shape, B, S, C)
+        ld = x.shape[1]
+        out = torch.empty(B, ld, device=x.device, dtype=torch.float32)
+        arg = torch.empty(B, ld, device=x.device, dtype=torch.int32)
+        check(lib().slide_col_max_seg(B, S, C, ld, ptr(x), ptr(out), ptr(arg), stream_of()), "slide_col_max_seg")
+        ctx.save_for_backward(arg)
+        ctx.cfg = (B, S)
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy, _darg):
+        (arg,) = ctx.saved_tensors
+        B, S = ctx.cfg
+        dy = dy.contiguous()
+        dx = torch.empty(B * S, arg.shape[1], device=dy.device, dtype=torch.float32)
+        check(lib().slide_col_max_seg_bwd(B, S, arg.shape[1], ptr(arg), ptr(dy), ptr(dx), stream_of()), "slide_col_max_seg_bwd")
+        return dx, None, None, None
+
+
+class GaussPosterior(torch.autograd.Function):
+    """DiagonalGaussianDistribution (pointnet2/data_utils/distributions.py:4-43) on rows: params [B * S, ldp] = [mean (C) | logvar (C)]
+    -> (z [B * S, ru(C)], kl [B]); z = mean + exp(0.5 clamp(logvar, -30, 20)) * eps, or the mode with eps None; kl = 0.5 * the sum over
+    the sample of mean^2 + var - 1 - clamp(logvar).  Differentiable in params; eps is a plain tensor [B * S, ru(C)] the caller draws
+    (the kernels never draw numbers: a captured step refills a static eps between replays)."""
+
+    @staticmethod
+    def forward(ctx, params, eps, B, S, C):
+        _chk(params)
+        assert params.shape[0] == B * S and 2 * C <= params.shape[1], (params.shape, B, S, C)
+        ldz = ru(C)
+        if eps is not None:
+            _chk(eps)
+            assert eps.shape == (B * S, ldz), (eps.shape, B, S, C)
+        z = torch.empty(B * S, ldz, device=params.device, dtype=torch.float32)
+        kl = torch.empty(B, device=params.device, dtype=torch.float32)
+        check(lib().slide_gauss_posterior_fwd(B, S, C, params.shape[1], ldz, ptr(params), ptr(eps), ptr(z), ptr(kl), stream_of()),
+              "slide_gauss_posterior_fwd")
+        ctx.save_for_backward(params, eps)
+        ctx.cfg = (B, S, C, ldz)
+        ctx.set_materialize_grads(False)  # an output nobody differentiates arrives as None: the kernel's NULL (that term is 0)
+        return z, kl
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dz, dkl):
+        params, eps = ctx.saved_tensors
+        B, S, C, ldz = ctx.cfg
+        dz = None if dz is None else dz.contiguous()
+        dkl = None if dkl is None else dkl.contiguous()
+        dparams = torch.empty_like(params)
+        check(lib().slide_gauss_posterior_bwd(B, S, C, params.shape[1], ldz, ptr(params), ptr(eps), ptr(dz), ptr(dkl), ptr(dparams),
+                                              stream_of()), "slide_gauss_posterior_bwd")
+        return dparams, None, None, None, None
+
+
+def col_max_seg(x, B, S, C):
+    """-> (max [B, ld], arg [B, ld] int32: the first row of the sample that attains it; -1 in the pad columns)"""
+    return ColMaxSeg.apply(x, B, S, C)
+
+
+def gauss_posterior(params, eps, B, S, C):
+    return GaussPosterior.apply(params, eps, B, S, C)
+
+
 def conv_rows(x, weight, bias=None):
     return ConvRows.apply(x, weight, bias)
 

@@ -1,7 +1,8 @@
 """Training losses of the two latent DDPMs, restated from the reference (forward = slide_amd.train.denoiser.TrainableDenoiser or any
 callable net(x_t, ts, label) -> eps prediction).  Random timesteps and noise are drawn here unless they are passed in (the parity
 tests inject the reference's); and the autoencoder's Chamfer losses (calc_cd_loss, autoencoder_losses) on the differentiable
-Chamfer sums of functions.ChamferCD, with the decode side's training loss on top (decoder_training_loss)."""
+Chamfer sums of functions.ChamferCD, with the decode side's training loss (decoder_training_loss) and the whole autoencoder's
+(autoencoder_training_loss) on top."""
 import numpy as np
 import torch
 
@@ -126,6 +127,28 @@ def autoencoder_losses(l_xyz_decoder, pointcloud, feature_weight, loss_type='cd_
     return loss_list
 
 
+def _sum_of_level_means(loss_list):
+    loss = loss_list[0]['training_loss'].mean()
+    for d in loss_list[1:]:
+        loss = loss + d['training_loss'].mean()
+    return loss
+
+
+def autoencoder_training_loss(ae, pointcloud, keypoint, label, eps=None, loss_type='cd_p', sample_posterior=True, fps_start_idx=None):
+    """the training loss of the whole autoencoder (slide_amd.train.encoder.TrainableAutoencoder): the reference's forward
+    (pointnet2/models/autoencoder.py:48-87: encode, the key-point level's posteriors and KL, decode, autoencoder_losses with the KL
+    term at the last level) and loss = the sum over the levels of training_loss.mean() (pointnet2/train_autoencoder.py:179-181).
+    -> (loss, loss_list); loss_list[-1] also carries 'feature_at_keypoint' (detached).  eps: the pair of standard-normal tensors of
+    the two posteriors (ae.posterior_shapes); None draws them with torch.randn on the device.  Capturable: under
+    GraphedTrainingStep pass static eps tensors and refill them (normal_()) between replays -- the kernels never draw numbers."""
+    l_xyz_decoder, feature_at_keypoint, kl = ae(pointcloud, keypoint, label, eps=eps, sample_posterior=sample_posterior,
+                                                fps_start_idx=fps_start_idx)
+    loss_list = autoencoder_losses(l_xyz_decoder, pointcloud, ae.feature_weight, loss_type=loss_type, kl_loss=kl, kl_weight=ae.kl_weight,
+                                   apply_kl_regularization=ae.apply_kl_regularization, fps_start_idx=fps_start_idx)
+    loss_list[-1]['feature_at_keypoint'] = feature_at_keypoint.detach()
+    return _sum_of_level_means(loss_list), loss_list
+
+
 def decoder_training_loss(decoder, keypoint, feature_at_keypoint, label, pointcloud, feature_weight, loss_type='cd_p', fps_start_idx=None):
     """the training loss of the decode side (slide_amd.train.decoder.TrainableDecoder): l_xyz_decoder = decoder.decode(keypoint,
     feature_at_keypoint, label), loss_list = autoencoder_losses on its levels against `pointcloud`, loss = the sum over the levels of
@@ -134,7 +157,4 @@ def decoder_training_loss(decoder, keypoint, feature_at_keypoint, label, pointcl
     with a fixed fps_start_idx tensor or None (drawn on the device)."""
     l_xyz_decoder = decoder.decode(keypoint, feature_at_keypoint, label, fps_start_idx=fps_start_idx)
     loss_list = autoencoder_losses(l_xyz_decoder, pointcloud, feature_weight, loss_type=loss_type, fps_start_idx=fps_start_idx)
-    loss = loss_list[0]['training_loss'].mean()
-    for d in loss_list[1:]:
-        loss = loss + d['training_loss'].mean()
-    return loss, loss_list
+    return _sum_of_level_means(loss_list), loss_list
