@@ -1230,44 +1230,60 @@ class DenoiserEngine:
         def finish(S):
             if isinstance(S, tuple):  # fused tail: scores GEMM + values GEMM + softmax-weighted sum in one launch
                 _, u, lay = S
-                vlay = gn_layout(cout)
-                Cp = ru(cout)
-                w5 = np.zeros((Cp, u.shape[1]), np.float32)
-                w5[np.ix_(np.arange(cout), lay.index)] = self._w(apfx + ".weight_conv.5.weight")
-                wv_l = self._w(apfx + ".feat_out_conv.0.weight")
-                wv = np.zeros((Cp, mo.shape[1]), np.float32)
-                wv[:cout, :wv_l.shape[1]] = wv_l
-                cmw = chunk_major if self.use_cm else (lambda w: w)
-                wdt = torch.float16 if self.prec == 1 else torch.float32  # (split tail: float row-major weights)
-                d = [self.A.put(cmw(w5), wdt), self.A.put(cmw(wv), wdt), self.A.put(self._tail_vectors(apfx, Cp))]
-                assert out.dtype == self.adt and u.dtype == self.adt and mo.dtype == self.adt and not self._is_cm(out)
-                assert self._is_fm(u) == self._is_fm(mo)
-                self._sync(1, 0)
-                self.flops += 2 * rows * (w5.size + wv.size)
-                out_cm = None
-                if self.use_cm and os.environ.get("SLIDE_CM_TABLES", "0") != "0" and npx_log2 == 8:  # (SA outputs feed gathers)
-                    out_cm = self._cm_copy[out.data_ptr()] = self.A.zeros(out.shape[0], out.shape[1], dtype=self.adt)
-                self._tail_of[out.data_ptr()] = self._emit(make_op(OP_ATTN_TAIL, i=(rows, self._ldp(u), u.shape[1], self._ldp(mo), mo.shape[1], Cp // 32, npx_log2,
-                                                    vlay.gs, vlay.n_norm, out.shape[1]),
-                                        # f[1]: 1 = chunk-major operands, + 2 = two-stage ring at three workgroups per CU (opt-in,
-                                        # SLIDE_TAIL_OCC3=1: measured neutral, 373.0 vs 372.3 shapes/s)
-                                        f=(1.0 / (vlay.gs_logical * npx), (1.0 if self.use_cm else 0.0) + (8.0 if self.prec != 1 else 0.0) +
-                                           (2.0 if os.environ.get("SLIDE_TAIL_OCC3", "0") != "0" else 0.0) +
-                                           (4.0 if (Cp // 32) % 4 == 0 and Cp // 32 >= int(os.environ.get("SLIDE_TAIL_WIDE", "1000")) else 0.0) +
-                                           (16.0 if self._is_fm(mo) else 0.0)),  # bit 4: u / mo fragment-major
-                                        p=(u.data_ptr(), d[0].data_ptr(), mo.data_ptr(), d[1].data_ptr(), out.data_ptr(),
-                                           d[2].data_ptr(), _dp(out_cm))),
-                    flops=2 * rows * cout * (len(lay.index) + wv_l.shape[1]),  # logical channels
-                    name=None if self.prec == 1 else "attn_tail_split_kernel<%d>" % npx_log2)
+                self._attn_tail(apfx, npx_log2, u, lay, mo, out)
                 return
-            # lane 0 (value branch), then the join
-            V = self._buf(rows, cout)
-            self._gemm(mo, npx_log2, [self._conv_gn_relu(apfx + ".feat_out_conv.0", apfx + ".feat_out_conv.1.group_norm", out=V)])
-            assert out.dtype == self.adt
-            self._sync(1, 0)
-            self._emit(make_op(OP_ATTN_COMBINE, i=(rows // K, cout, S.shape[1], V.shape[1], out.shape[1], K, self.prec),
-                                    p=(S.data_ptr(), V.data_ptr(), out.data_ptr())))
+            self._attn_combine(apfx, npx_log2, S, mo, out)
         return (finish_scores, finish), cout
+
+    def _attn_tail(self, apfx, npx_log2, u, lay, mo, out):
+        """the fused end of an AttentionModule as ONE launch (SLIDE_OP_ATTN_TAIL: csrc/attn_tail.hip in fp16, csrc/gemm_gxs.hip in the
+        split arithmetic): scores W5 . u + b5 (u: the intermediate layer's output in its PADDED GroupNorm layout `lay`), values
+        relu(GN(Wv . mo + bv)), out[point] = sum_k softmax_k(scores) * values.  Returns the launch"""
+        cout = self.sd[apfx + ".weight_conv.5.weight"].shape[0]
+        rows, npx = self.B * 16 << (npx_log2 - 4), 1 << npx_log2
+        vlay = gn_layout(cout)
+        Cp = ru(cout)
+        w5 = np.zeros((Cp, u.shape[1]), np.float32)
+        w5[np.ix_(np.arange(cout), lay.index)] = self._w(apfx + ".weight_conv.5.weight")
+        wv_l = self._w(apfx + ".feat_out_conv.0.weight")
+        wv = np.zeros((Cp, mo.shape[1]), np.float32)
+        wv[:cout, :wv_l.shape[1]] = wv_l
+        cmw = chunk_major if self.use_cm else (lambda w: w)
+        wdt = torch.float16 if self.prec == 1 else torch.float32  # (split tail: float row-major weights)
+        d = [self.A.put(cmw(w5), wdt), self.A.put(cmw(wv), wdt), self.A.put(self._tail_vectors(apfx, Cp))]
+        assert out.dtype == self.adt and u.dtype == self.adt and mo.dtype == self.adt and not self._is_cm(out)
+        assert self._is_fm(u) == self._is_fm(mo)
+        self._sync(1, 0)
+        self.flops += 2 * rows * (w5.size + wv.size)
+        out_cm = None
+        if self.use_cm and os.environ.get("SLIDE_CM_TABLES", "0") != "0" and npx_log2 == 8:  # (SA outputs feed gathers)
+            out_cm = self._cm_copy[out.data_ptr()] = self.A.zeros(out.shape[0], out.shape[1], dtype=self.adt)
+        self._tail_of[out.data_ptr()] = self._emit(make_op(OP_ATTN_TAIL, i=(rows, self._ldp(u), u.shape[1], self._ldp(mo), mo.shape[1], Cp // 32, npx_log2,
+                                            vlay.gs, vlay.n_norm, out.shape[1]),
+                                # f[1]: 1 = chunk-major operands, + 2 = two-stage ring at three workgroups per CU (opt-in,
+                                # SLIDE_TAIL_OCC3=1: measured neutral, 373.0 vs 372.3 shapes/s)
+                                f=(1.0 / (vlay.gs_logical * npx), (1.0 if self.use_cm else 0.0) + (8.0 if self.prec != 1 else 0.0) +
+                                   (2.0 if os.environ.get("SLIDE_TAIL_OCC3", "0") != "0" else 0.0) +
+                                   (4.0 if (Cp // 32) % 4 == 0 and Cp // 32 >= int(os.environ.get("SLIDE_TAIL_WIDE", "1000")) else 0.0) +
+                                   (16.0 if self._is_fm(mo) else 0.0)),  # bit 4: u / mo fragment-major
+                                p=(u.data_ptr(), d[0].data_ptr(), mo.data_ptr(), d[1].data_ptr(), out.data_ptr(),
+                                   d[2].data_ptr(), _dp(out_cm))),
+            flops=2 * rows * cout * (len(lay.index) + wv_l.shape[1]),  # logical channels
+            name=None if self.prec == 1 else "attn_tail_split_kernel<%d>" % npx_log2)
+        return self._tail_of[out.data_ptr()]
+
+    def _attn_combine(self, apfx, npx_log2, S, mo, out):
+        """the three-launch end of an AttentionModule, after the scores GEMM that wrote S: the values GEMM (lane 0), the join, and the
+        softmax-weighted sum over a point's K rows (SLIDE_OP_ATTN_COMBINE).  Returns the combine launch"""
+        cout = self.sd[apfx + ".weight_conv.5.weight"].shape[0]
+        K = 1 << (npx_log2 - 4)
+        rows = self.B * 16 * K
+        V = self._buf(rows, cout)
+        self._gemm(mo, npx_log2, [self._conv_gn_relu(apfx + ".feat_out_conv.0", apfx + ".feat_out_conv.1.group_norm", out=V)])
+        assert out.dtype == self.adt
+        self._sync(1, 0)
+        return self._emit(make_op(OP_ATTN_COMBINE, i=(rows // K, cout, S.shape[1], V.shape[1], out.shape[1], K, self.prec),
+                                  p=(S.data_ptr(), V.data_ptr(), out.data_ptr())))
 
     def _grouped_input(self, kind, feat_in, C, Cg, K):
         """the grouped input of an SA / FP block.  fp16 LDS-DMA path: only the last chunks (left-over feature columns +
