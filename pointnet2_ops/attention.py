@@ -3,13 +3,11 @@ AttentionModule (:35-96, vector attention over the K neighbours), GlobalAttentio
 signatures and state-dict names.  AttentionModule runs row-major (slide_amd.rows: GEMMs on [B * np * K][C] matrices, in-place
 GroupNorm passes, one softmax-reduction kernel); GlobalAttentionModule (N x N scores, unused by the shipped configs) is a
 tensor program over the HIP convolution / GroupNorm kernels."""
-import os
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from slide_amd import rows as R
+from slide_amd import knobs, rows as R
 from slide_amd.nn_ops import HipConv1x1, HipGroupNorm
 
 
@@ -61,7 +59,7 @@ class AttentionModule(nn.Module):
         Saves the concat + ReLU pass, the statistics pass over it and C1 / (C1 + C2) of the consumer GEMM's input bytes.  None when the
         shapes do not qualify (fp32 module mode, samples that are not whole 256-row tiles, K not a power of two): the caller concatenates."""
         if not (R.deferral() and R.fused_stats() and query.half and grouped.S % 256 == 0 and K & (K - 1) == 0
-                and grouped.rows == query.rows * K and query.rows > 0 and os.environ.get("SLIDE_MODULE_SPLIT_QK", "1") != "0"):
+                and grouped.rows == query.rows * K and query.rows > 0 and knobs.read("SLIDE_MODULE_SPLIT_QK")):
             return None
         if query.S % 256 == 0:
             q1 = R.conv(query, self.feat_conv, stats="relu")

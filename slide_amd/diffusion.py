@@ -11,7 +11,6 @@ Noise is either an explicit tensor (parity tests inject the reference's stream) 
 (Philox4x32-10 + Box-Muller keyed on (seed, step, element)).
 """
 import ctypes
-import os
 import weakref
 
 import numpy as np
@@ -134,8 +133,9 @@ class _GraphedSampler:
         self.use_graph = use_graph
         # (experiment knob SLIDE_STREAM_PRIO="<position>,<feature>": HIP stream priorities of the chains, -1 = high, 0 = default)
         prio = 0
-        if os.environ.get("SLIDE_STREAM_PRIO"):
-            pp = [int(v) for v in os.environ["SLIDE_STREAM_PRIO"].split(",")]
+        knobs = self.engine.knobs
+        if knobs.SLIDE_STREAM_PRIO:
+            pp = [int(v) for v in knobs.SLIDE_STREAM_PRIO.split(",")]
             prio = pp[0] if hp.get("in_fea_dim", 0) == 0 else pp[-1]
         # stream: run this chain on an existing stream (a second sampler of one chain slot: the runtime maps streams onto the four
         # hardware queues in creation order, so taking another pool stream would shift every later sampler's queue)
@@ -149,14 +149,14 @@ class _GraphedSampler:
         # cu_share: run this chain's kernels on that fraction of the compute units only (SLIDE_POS_CUS / SLIDE_FEAT_CUS=<n> override it
         # for the position / feature chains; 0 = all).  The position chain beside the feature sub-batches is given 11/16 of the chip:
         # its wide split launches then never take EVERY CU from the latency-critical feature chains
-        env_cus = os.environ.get("SLIDE_POS_CUS" if hp.get("in_fea_dim", 0) == 0 else "SLIDE_FEAT_CUS")
+        env_cus = knobs.SLIDE_POS_CUS if hp.get("in_fea_dim", 0) == 0 else knobs.SLIDE_FEAT_CUS
         ncu = int(env_cus) if env_cus is not None else (
             int(torch.cuda.get_device_properties(device).multi_processor_count * cu_share) if (cu_share and device.type == "cuda") else 0)
         if ncu > 0 and device.type == "cuda":
             # a stream confined to `ncu` compute units (slide_stream_create_cu_mask): SLIDE_POS_CUS for the position chains,
             # SLIDE_FEAT_CUS for the feature chains; SLIDE_CU_MASK_FROM=<first CU> (default 0)
             total = torch.cuda.get_device_properties(device).multi_processor_count
-            first = int(os.environ.get("SLIDE_CU_MASK_FROM", "0"))
+            first = knobs.SLIDE_CU_MASK_FROM
             words = [0] * ((total + 31) // 32)
             for cu in range(first, min(first + ncu, total)):
                 words[cu // 32] |= 1 << (cu % 32)
@@ -186,7 +186,7 @@ class _GraphedSampler:
         # the new state (per-point table, concatenation columns), so SLIDE_OP_PREP_POINTS -- coordinates and neighbour tables,
         # constant over the chain -- runs once per chain in begin() instead of once per step (SLIDE_FUSE_PREP=0: per step)
         self.fuse_prep = False
-        if (fixed_xyz and update_op.kind == OP_UPDATE_FEAT and os.environ.get("SLIDE_FUSE_PREP", "1") != "0"
+        if (fixed_xyz and update_op.kind == OP_UPDATE_FEAT and e.knobs.SLIDE_FUSE_PREP
                 and e.ops[e._prep_idx].p[5] is None):  # (no chunk-major second copy of the table)
             prep = e.ops[e._prep_idx]
             assert prep.kind == OP_PREP_POINTS
@@ -200,7 +200,7 @@ class _GraphedSampler:
         # step instead of 105, but 384.1 vs 389.4 shapes/s: one workgroup per four samples runs the layers, the Philox draws and
         # the state update of 3264 elements in sequence, where the three launches spread them over 22 + 44 + 71 workgroups
         head = getattr(e, "head", None)
-        if (head is not None and os.environ.get("SLIDE_HEAD_UPDATE", "0") != "0" and update_op.kind in (OP_UPDATE_POS, OP_UPDATE_FEAT)
+        if (head is not None and e.knobs.SLIDE_HEAD_UPDATE and update_op.kind in (OP_UPDATE_POS, OP_UPDATE_FEAT)
                 and e.ops[head["idx"][0]].kind == OP_GEMM and e.ops[head["idx"][1]].kind == OP_GEMM and head["idx"][1] == e.eps_copy_idx - 1):
             h, u = SlideHeadArgs(), update_op
             h.X, h.W0, h.W1, h.v0, h.b1 = (head[k_].data_ptr() for k_ in ("X", "W0", "W1", "v0", "b1"))
@@ -220,14 +220,14 @@ class _GraphedSampler:
             # chain's loads -- measured SLOWER (382.8 vs 389.8 shapes/s, three alternating pairs; the launch 18.7 -> 45.8 us): the
             # Box-Muller draws (precise logf / cosf) and the update's scattered 4-byte stores of 1632 elements on 256 threads
             # outweigh the 71-workgroup update launch they replace, as they did in round 4's head_update_kernel
-            if update_op.kind == OP_UPDATE_FEAT and os.environ.get("SLIDE_POINT_CHAIN_UPDATE", "0") != "0":
+            if update_op.kind == OP_UPDATE_FEAT and e.knobs.SLIDE_POINT_CHAIN_UPDATE:
                 _copy_update(c.upd, update_op)
                 c.fuse_update = 1
                 update_op = None
             self._chain_args = c  # (kept alive: the op carries its address)
             chain_at = pch["idx"][0]
             drop = drop | set(pch["idx"][1:])
-        abl = os.environ.get("SLIDE_ABL_DROP")
+        abl = e.knobs.SLIDE_ABL_DROP
         if abl:  # TIMING ablation (tools/ab/r05_ablate.sh): the launches whose kernel name contains one of the substrings are left out -- wrong results
             names = getattr(e, "kernel_names", {})
             lab = lambda i: names.get(i, "") + (" gemm16" if e.ops[i].kind == OP_GEMM and e.ops[i].i[0] == 16 * e.B else "") + \

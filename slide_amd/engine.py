@@ -10,12 +10,12 @@ bias, res_connect, no condition cloud).  The plan is replayed eagerly or from a 
 torch is used for device memory and streams only; all arithmetic runs in libslide_hip.so.
 """
 import ctypes
-import os
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
+from . import knobs
 from ._lib import SlideHipError, check, lib
 # the C side of include/slide_engine.h -- every OP_* / EPI_* / F_* constant, PREC, the struct mirrors, make_op and ru -- is declared
 # in abi.py; all of it stays importable from this module
@@ -277,8 +277,8 @@ class DenoiserEngine:
         self.per_sample_t = per_sample_t
         self.t_table = int(t_table)
         assert per_sample_t or t_table > 0
-        self.use_glds = os.environ.get("SLIDE_GLDS", "1") != "0"  # LDS-DMA GEMM variant for fp16 GEMMs
-        self.glds_nst = int(os.environ.get("SLIDE_GLDS_WIDE", "0"))  # 1: 64-deep K chunks (full cache lines)
+        self.use_glds = self.knobs.SLIDE_GLDS  # LDS-DMA GEMM variant for fp16 GEMMs
+        self.glds_nst = self.knobs.SLIDE_GLDS_WIDE  # 1: 64-deep K chunks (full cache lines)
         self.sd = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)).astype(np.float32)
                    for k, v in state_dict.items()}
         arch = hp["architecture"]
@@ -292,14 +292,14 @@ class DenoiserEngine:
         self.out_dim = hp["out_dim"]
         self.t_dim = hp["t_dim"]
         # chunk-major activations / weights for the 128- and 256-row ring kernels (SLIDE_CM=0: row-major everywhere, A/B)
-        self.use_cm = (self.prec == 1 and self.use_glds and self.glds_nst != 1 and os.environ.get("SLIDE_CM", "1") != "0"
-                       and not os.environ.get("SLIDE_XS", ""))
+        self.use_cm = (self.prec == 1 and self.use_glds and self.glds_nst != 1 and self.knobs.SLIDE_CM
+                       and not self.knobs.SLIDE_XS)
         # pair decomposition of the blocks' first layers + generated-X GEMMs (csrc/gemm_gx.hip; SLIDE_GX=0: the round-2 plan)
-        self.use_gx = self.use_cm and os.environ.get("SLIDE_GX", "1") != "0"
+        self.use_gx = self.use_cm and self.knobs.SLIDE_GX
         # round 5: the pair decomposition in the SPLIT arithmetic (csrc/gemm_gxs.hip): float pair tables, generated-X split GEMMs,
         # PAIR residuals on float rows, the split attention tail -- the K-expanded first-layer outputs, scores and values of a block
         # never reach memory (SLIDE_GXS=0: the fp32-structured plan of round 4)
-        self.use_gxs = self.prec == 2 and os.environ.get("SLIDE_GXS", "1") != "0"
+        self.use_gxs = self.prec == 2 and self.knobs.SLIDE_GXS
         if self.use_gxs:
             # its kernels run the split products on ONE accumulator set with the weight's high term scaled by 2^11 in fp16 (DESIGN.md
             # section 5): exact while |w| < 32.  A checkpoint with a larger convolution weight takes the fp32-structured split plan.
@@ -312,14 +312,18 @@ class DenoiserEngine:
         self._cm = set()
         self._fm = set()  # chunk-major buffers whose 32-row groups are fragment-major (_tail_fm)
         self._cm_copy = {}  # per-point table (data_ptr) -> its chunk-major copy, written by the table's producer as well
-        self.two_lanes = os.environ.get("SLIDE_TWO_LANES", "0") != "0"  # measured: no gain at batch 256
+        self.two_lanes = self.knobs.SLIDE_TWO_LANES  # measured: no gain at batch 256
         self._tvec = []   # (name, width) of every Mlp .fc           -> offsets into the t vector
         self._cvec = []   # (name, width) of every Mlp .fc_condition -> offsets into the condition vector
         self._build()
 
     def _plan_state(self, batch, device, prec):
         """the state the emitters below read and write while a plan is built; bare builders (one-op tests and tools) call this in
-        place of __init__.  The knobs are at their defaults here: __init__ / _build read the environment"""
+        place of __init__.  Resolves every plan knob from the environment, once, into `self.knobs` (knobs.snapshot): nothing in this
+        module reads the environment after that, so the emitters of a bare builder see SLIDE_GX_N64 and the like as they are now.
+        Pins the derived attributes `use_glds`, `glds_nst`, `persistent` and `two_lanes` at their defaults, whatever the snapshot
+        says: __init__ / _build set them from it (and `use_cm`, `use_gx`, `use_gxs`, `fold_copies`), bare builders assign them."""
+        self.knobs = knobs.snapshot()
         self.B, self.device, self.prec = int(batch), device, PREC[prec]
         self.adt = torch.float16 if self.prec == 1 else torch.float32  # activation storage type
         self.A = _Arena(device)
@@ -360,15 +364,15 @@ class DenoiserEngine:
         attn_tail_rx_kernel for it: fp16 pair-decomposition plan (its generated-X kernels and the SA chain are the producers that
         can store the layout), fused tail, values' chunk count a multiple of 4, none
         of the opt-in tail forms.  SLIDE_FM=0: chunk-major u / mo (A/B)."""
-        env = os.environ.get
+        k = self.knobs
         cout = self.sd[apfx + ".weight_conv.5.weight"].shape[0]
         # mo's producer must be one that stores the layout: the generated-X GEMM of a two-layer Mlp, or the SA chain -- a rest_mlp
         # outside the chain is a ring GEMM over a stored h2 (gemm_ring.hip: its epilogue instantiations do not carry the layout)
         if (mpfx + ".rest_mlp.0.weight") in self.sd and not self._sa_chain_shapes(mpfx, npx_log2):
             return False
-        return bool(self.use_cm and self.use_gx and self.prec == 1 and self.use_glds and env("SLIDE_FM", "1") != "0"
-                    and env("SLIDE_ATTN_TAIL", "1") != "0" and env("SLIDE_TAIL_RX", "1") != "0" and env("SLIDE_TAIL8", "0") == "0"
-                    and env("SLIDE_TAIL_OCC3", "0") == "0" and "SLIDE_TAIL_WIDE" not in os.environ and env("SLIDE_BODY", "0") == "0"
+        return bool(self.use_cm and self.use_gx and self.prec == 1 and self.use_glds and k.SLIDE_FM
+                    and k.SLIDE_ATTN_TAIL and k.SLIDE_TAIL_RX and not k.SLIDE_TAIL8
+                    and not k.SLIDE_TAIL_OCC3 and k.SLIDE_TAIL_WIDE is None and k.SLIDE_BODY == "0"
                     and npx_log2 in (7, 8) and (ru(n_mo) // 32) % 4 == 0 and gn_layout(cout).unpermuted)
 
     def _ldp(self, t):
@@ -530,7 +534,7 @@ class DenoiserEngine:
         # of every block in every workgroup's prologue (SLIDE_PACKED_VECS=0: plain pointer, A/B)
         epis, pv = self._pack_epi(segs, 1 << npx_log2, rows, npx_log2, **epi_kw)
         ed = self.A.put(np.concatenate([epis, pv.reshape(-1).view(np.uint8)]))
-        edp = ed.data_ptr() | (1 if os.environ.get("SLIDE_PACKED_VECS", "1") != "0" else 0)
+        edp = ed.data_ptr() | (1 if self.knobs.SLIDE_PACKED_VECS else 0)
         return _Layer(segs, widths, W, Wd, w_cm, ed, edp, W.shape[0] // 32, ld, rows, 2 * rows * sum(int(sg["w"].size) for sg in segs))
 
     def _gemm(self, X, npx_log2, segs, in_cols=None, in_affine=None, gather=None, gn_fin=None,
@@ -586,9 +590,9 @@ class DenoiserEngine:
         assert X.dtype == self.adt
         # wide (128-channel) tiles only when the grid still covers the 256 CUs at least twice
         ntr = (rows + 255) // 256
-        cbw = 4 if (self.prec == 1 and n_cob >= 4 and ntr * ((n_cob + 3) // 4) >= int(os.environ.get('SLIDE_CBW4_TILES', '1000'))) else 2
+        cbw = 4 if (self.prec == 1 and n_cob >= 4 and ntr * ((n_cob + 3) // 4) >= self.knobs.SLIDE_CBW4_TILES) else 2
         # narrow launches: 32-channel tiles double the workgroups and halve each wave's epilogue while they still fit one round
-        if (self.prec == 1 and self.use_glds and sc is None and npx_log2 >= 7 and ntr * n_cob <= int(os.environ.get('SLIDE_CBW1_TILES', '0'))):
+        if self.prec == 1 and self.use_glds and sc is None and npx_log2 >= 7 and ntr * n_cob <= self.knobs.SLIDE_CBW1_TILES:
             cbw = 1
         esz = X.element_size()
         rd = rows * ld * esz + L.W.size * esz + sum(rows * n * esz for sg, n in zip(L.segs, L.widths) if sg.get("residual") is not None)
@@ -607,22 +611,22 @@ class DenoiserEngine:
         # SLIDE_XS = "" (default: off) | "auto" (gathered layers + plain layers with >= 8 column tiles per workgroup) |
         # "7,8" (every eligible layer of those sample sizes).
         wfrag = None
-        xs_mode = os.environ.get("SLIDE_XS", "")
+        xs_mode = self.knobs.SLIDE_XS
         xs_levels = {7, 8} if xs_mode == "auto" else {int(v) for v in xs_mode.split(",") if v}
         xs_lds = ((ld - (gather.chunks * 32 if gather is not None else 0)) // 32) * 16384  # resident X rows (gathered chunks: 1 KB each)
         if (glds and npx_log2 in xs_levels and gn_fin is None and not (gather is not None and sc is not None)
                 and xs_lds + 20 * 1024 <= 160 * 1024):
             if xs_mode != "auto" or gather is not None or (npx_log2 == 8 and sc is None and n_cob >= 16 and xs_lds > 96 * 1024):
                 wfrag = Wd  # (selects the kernel; it reads the same row-major weights)
-                cbw = 4 if n_cob >= 4 and os.environ.get("SLIDE_XS_CBW", "2") == "4" else 2
+                cbw = 4 if n_cob >= 4 and self.knobs.SLIDE_XS_CBW == "4" else 2
         gtab = None if gather is None else self._cm_copy.get(gather.table.data_ptr(), gather.table)  # chunk-major copy: g_ldf == 32
         assert wfrag is None or gtab is None or gtab is gather.table
         gf = (0.0, 0.0, 0.0) if gather is None else (float(gather.chunks), float(32 if gtab is not gather.table else gather.table.shape[1]),
                                                      float({8: 3, 16: 4}[gather.K]))
         knob = self.glds_nst
         assert wfrag is None or not (w_cm or self._is_cm(X))
-        if wfrag is not None and os.environ.get("SLIDE_XS_OCC"):
-            knob = 10 + int(os.environ["SLIDE_XS_OCC"])  # cap the workgroups per CU of the X-stationary kernel (A/B timing)
+        if wfrag is not None and self.knobs.SLIDE_XS_OCC:
+            knob = 10 + int(self.knobs.SLIDE_XS_OCC)  # cap the workgroups per CU of the X-stationary kernel (A/B timing)
         has_pair = any(sg["res_pair"] is not None for sg in L.segs)  # -> the kernels compiled with the PAIR residual
         # (a per-point layer of a split plan: _merge_pp may fold it into a SLIDE_OP_PP_STAGE launch, from its float weights)
         pp = (self.use_gxs and npx_log2 == 4 and gather is None and gn_fin is None and pre_gather is None and wfrag is None and
@@ -632,7 +636,7 @@ class DenoiserEngine:
         self.flops += L.flops
         return self._emit(make_op(OP_GEMM, i=(rows, self._ldp(X), ld, n_cob, npx_log2, 0 if in_affine is None else in_affine.bs, self.prec, cbw,
                                               glds | (2 if w_cm else 0) | (4 if has_pair else 0), knob),
-                                  f=(-1.0 if self.persistent == 2 else float(os.environ.get('SLIDE_STAGGER_US', '0')),) + gf,
+                                  f=(-1.0 if self.persistent == 2 else self.knobs.SLIDE_STAGGER_US,) + gf,
                                   p=self._affine_ptrs(X.data_ptr(), Wd.data_ptr(), L.epi_ptr, in_affine) + (None, _dp(gn_fin),
                                      self._sched().data_ptr() if self.persistent else None, _dp(gtab),
                                      _dp(gather.nbr if gather is not None else pre_gather if pair_tabs is None else nbr),
@@ -673,11 +677,11 @@ class DenoiserEngine:
         # (LDS of the 64-channel form: ring stages of 8 KB of weights + 4 KB of streamed table images per sample, epilogue
         #  descriptors, per-sample vectors; three stages, else two)
         shm64 = lambda nst: nst * (8192 + 4096 * nsamp) + (2 * 40 + 2 * 96) * 4 + nsamp * nvec * ld * 2 + 16
-        knob = os.environ.get("SLIDE_GX_N64", "1")
+        knob = self.knobs.SLIDE_GX_N64
         n64, nst = 0, 3
         if knob != "0" and gx["mode"] == 1 and shm64(3) <= 53 * 1024:
             n64 = 1
-        elif knob != "0" and os.environ.get("SLIDE_GX_N64W", "1") != "0" and (
+        elif knob != "0" and self.knobs.SLIDE_GX_N64W and (
                 n_cob <= 2 or ((rows + 255) // 256) * ((n_cob + 3) // 4) <= 256):
             # (n_cob <= 2 -- the position net's 32- / 64-channel layers: a 128-channel tile would be half empty)
             # where the 128-channel grid would leave CUs empty -- the FP blocks at 88 samples: 96 workgroups -- 64-channel tiles at
@@ -760,7 +764,7 @@ class DenoiserEngine:
             assert gn_layout(c2).unpermuted, "second_mlp width with padded GroupNorm groups"
             seg3 = with_res(self._conv_gn_relu(pfx + ".rest_mlp.0", pfx + ".rest_mlp.1.group_norm", out=final_out, out_coff=final_coff))
         if (has_rest and pair is not None and self.use_gxs and npx_log2 == 8 and ru(gn_layout(c2).width) <= 64
-                and os.environ.get("SLIDE_GXS_CHAIN", "1") != "0"):
+                and self.knobs.SLIDE_GXS_CHAIN):
             # split plans (round 5): second_mlp -> rest_mlp of an SA block in ONE launch -- h2 stays in the generated-X kernel's
             # accumulators and feeds rest_mlp's contraction from there (csrc/gemm_gxs.hip, CHAIN); needs every channel of h2 in
             # one 64-channel tile.  SLIDE_GXS_CHAIN=0: two launches and an h2 round trip
@@ -783,7 +787,7 @@ class DenoiserEngine:
     def _sa_chain_shapes(self, pfx, npx_log2):
         """does SLIDE_OP_SA_CHAIN cover this Mlp's second_mlp -> rest_mlp (widths, identity GroupNorm layouts, group sizes)?"""
         sd = self.sd
-        if (npx_log2 != 8 or os.environ.get("SLIDE_SA_CHAIN", "1") == "0" or self.prec != 1 or not self.use_gx
+        if (npx_log2 != 8 or not self.knobs.SLIDE_SA_CHAIN or self.prec != 1 or not self.use_gx
                 or (pfx + ".rest_mlp.0.weight") not in sd):
             return False
         c1 = sd[pfx + ".first_mlp.0.weight"].shape[0]
@@ -857,7 +861,7 @@ class DenoiserEngine:
         offs, ldy = seg_offsets(segs)
         # SLIDE_PAIR_FUSED (default on): the per-point GEMM and the pair-table pass as ONE launch (SLIDE_OP_PAIR_FIRST,
         # csrc/gemm_ring.hip pair_first_kernel) -- y never goes through memory; bit-identical to the two-launch form
-        fused = fin is None and self.prec == 1 and self.use_glds and os.environ.get("SLIDE_PAIR_FUSED", "1") != "0"
+        fused = fin is None and self.prec == 1 and self.use_glds and self.knobs.SLIDE_PAIR_FUSED
         Y = None if fused else self.A.zeros(B * 16, ldy)  # fp32
         wa, wb, vv_in = np.zeros((ldy, 4), np.float32), np.zeros((ldy, 4), np.float32), np.zeros((2, ldy), np.float32)
         psegs = []
@@ -903,7 +907,7 @@ class DenoiserEngine:
             self._gemm(feat_in, 4, list(lead_segs) + ysegs)
             ed = self._epi_only(psegs, 1 << npx_log2)
             # loop-invariant when the coordinates are a fixed condition?  No: y changes every step.
-            v2 = ldy <= 2048 and (os.environ.get("SLIDE_PAIR_NORM_V2", "0") != "0" or self.prec != 1)
+            v2 = ldy <= 2048 and (self.knobs.SLIDE_PAIR_NORM_V2 or self.prec != 1)
             assert (fin is None or v2) and (self.prec == 1 or v2)
             self._emit(make_op(OP_PAIR_NORM, i=(B, ldy, K, 2 if v2 else 1, int(self.prec != 1)),
                                p=(Y.data_ptr(), self.xyz.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), ed.data_ptr(),
@@ -921,7 +925,7 @@ class DenoiserEngine:
         # OPT-IN since round 5 (SLIDE_BODY=1, experiments build): with the split position plan beside the feature chains the one-launch
         # body of the FP0-sized blocks LOSES 0.9 % to its three separate launches (378.5 vs 382.0 shapes/s, four alternating pairs) --
         # one workgroup per CU at 0.024 MFMA-busy holds a CU for 31 us where the ring kernels' small workgroups interleave
-        if not self.use_gx or os.environ.get("SLIDE_BODY", "0") == "0":
+        if not self.use_gx or self.knobs.SLIDE_BODY == "0":
             return None
         rest = (mpfx + ".rest_mlp.0.weight") in sd
         c1 = sd[mpfx + ".first_mlp.0.weight"].shape[0]
@@ -939,7 +943,7 @@ class DenoiserEngine:
         shape = (npx_log2, rest, (c2 // 32) if rest else 0, n_mo // 32, n_u // 32)
         # ((7, False, 0, 8, 8) -- FP1 -- was built and measured slower than its three separate launches: one wave per SIMD)
         # ((8, True, 4, 8, 5) -- SA0 -- spills under its 256-register budget: opt-in with SLIDE_BODY=2)
-        if shape not in (((7, False, 0, 4, 4), (8, True, 4, 8, 5)) if os.environ.get("SLIDE_BODY", "0") == "2" else ((7, False, 0, 4, 4),)):
+        if shape not in (((7, False, 0, 4, 4), (8, True, 4, 8, 5)) if self.knobs.SLIDE_BODY == "2" else ((7, False, 0, 4, 4),)):
             return None
         return shape
 
@@ -1139,7 +1143,7 @@ class DenoiserEngine:
             # the per-sample table pass also finalises the joint GroupNorm (SLIDE_OP_PAIR_NORM version 2)
             # (SLIDE_PAIR_NORM_V2=1, opt-in: one 1024-thread workgroup per sample that also finalises the joint GroupNorm -- 3 %
             #  faster for a single chain, 5 % slower with four chains in flight: sixteen waves must find room on ONE CU)
-            pair_fin = ldT <= 2048 and (os.environ.get("SLIDE_PAIR_NORM_V2", "0") != "0" or self.use_gxs)
+            pair_fin = ldT <= 2048 and (self.knobs.SLIDE_PAIR_NORM_V2 or self.use_gxs)
             ctx = self._pair_first(npx_log2, K, feat_tab, Cf, [mlp_first, mlp_res, kseg], coords,
                                    fin=fin_struct() if pair_fin else None,
                                    lead_segs=([qctx["qseg"]] + [e["qseg"] for e in extra_q]) if q_rides else ())
@@ -1150,7 +1154,7 @@ class DenoiserEngine:
             if K == 8:  # coefficient vectors of the two per-slot scalars for the res_connect channels (RAW segment: unscaled)
                 ctx["rvv"] = self.A.put(np.ascontiguousarray(ctx["vv_in"][:, ctx["offr"]:ctx["offr"] + rres]))
             self.pair_ctx = ctx
-        elif gather is not None and gather.chunks * 32 >= int(os.environ.get("SLIDE_SPLIT_FIRST", "1000000")):
+        elif gather is not None and gather.chunks * 32 >= self.knobs.SLIDE_SPLIT_FIRST:
             # (opt-in, SLIDE_SPLIT_FIRST=<min feature channels>: measured neutral to -1.5 % on the feature plan -- the
             # 256-row launch is bound by its epilogue, not by its K loop, and the per-point GEMM is one more launch)
             # The layer is linear in its input and the leading Cf input channels of row (point, neighbour) are the
@@ -1177,7 +1181,7 @@ class DenoiserEngine:
             d = fin_d
             # (only the small-launch kernel finalises: same grid bound as run_gemm's dispatch)
             n_cob_p = ru(gn_layout(inter).width) // 32
-            fuse_fin = (self.prec == 1 and self.use_glds and os.environ.get("SLIDE_FUSE_FIN", "1") != "0" and
+            fuse_fin = (self.prec == 1 and self.use_glds and self.knobs.SLIDE_FUSE_FIN and
                         ((B * 16 + 63) // 64) * ((n_cob_p + 1) // 2) <= 1024)
             gn_fin = None
             if pair_fin:
@@ -1212,12 +1216,12 @@ class DenoiserEngine:
             else:
                 self._gemm(Tk, npx_log2, [useg], in_affine=InAffine(scale, shift, C1p, ldT))
             vlay = gn_layout(cout)
-            if (self.prec == 1 and self.use_glds and os.environ.get("SLIDE_ATTN_TAIL", "1") != "0" and vlay.unpermuted):
+            if (self.prec == 1 and self.use_glds and self.knobs.SLIDE_ATTN_TAIL and vlay.unpermuted):
                 self._lane = 0
                 return ("fused", u, lay)  # scores are computed inside the fused attention tail (finish)
             # round 5: the same tail in the split arithmetic on float rows (csrc/gemm_gxs.hip attn_tail_split_kernel;
             # SLIDE_TAIL_SPLIT=0: scores GEMM + values GEMM + combine launch).  Its single-accumulator split needs |w| < 32.
-            if (self.use_gxs and os.environ.get("SLIDE_TAIL_SPLIT", "1") != "0" and vlay.unpermuted
+            if (self.use_gxs and self.knobs.SLIDE_TAIL_SPLIT and vlay.unpermuted
                     and self._split1_ok(self._w(apfx + ".weight_conv.5.weight"), self._w(apfx + ".feat_out_conv.0.weight"))):
                 self._lane = 0
                 return ("fused", u, lay)
@@ -1255,16 +1259,17 @@ class DenoiserEngine:
         assert self._is_fm(u) == self._is_fm(mo)
         self._sync(1, 0)
         self.flops += 2 * rows * (w5.size + wv.size)
+        wide_from = 1000 if self.knobs.SLIDE_TAIL_WIDE is None else int(self.knobs.SLIDE_TAIL_WIDE)  # (channel blocks; unset: no layer)
         out_cm = None
-        if self.use_cm and os.environ.get("SLIDE_CM_TABLES", "0") != "0" and npx_log2 == 8:  # (SA outputs feed gathers)
+        if self.use_cm and self.knobs.SLIDE_CM_TABLES and npx_log2 == 8:  # (SA outputs feed gathers)
             out_cm = self._cm_copy[out.data_ptr()] = self.A.zeros(out.shape[0], out.shape[1], dtype=self.adt)
         self._tail_of[out.data_ptr()] = self._emit(make_op(OP_ATTN_TAIL, i=(rows, self._ldp(u), u.shape[1], self._ldp(mo), mo.shape[1], Cp // 32, npx_log2,
                                             vlay.gs, vlay.n_norm, out.shape[1]),
                                 # f[1]: 1 = chunk-major operands, + 2 = two-stage ring at three workgroups per CU (opt-in,
                                 # SLIDE_TAIL_OCC3=1: measured neutral, 373.0 vs 372.3 shapes/s)
                                 f=(1.0 / (vlay.gs_logical * npx), (1.0 if self.use_cm else 0.0) + (8.0 if self.prec != 1 else 0.0) +
-                                   (2.0 if os.environ.get("SLIDE_TAIL_OCC3", "0") != "0" else 0.0) +
-                                   (4.0 if (Cp // 32) % 4 == 0 and Cp // 32 >= int(os.environ.get("SLIDE_TAIL_WIDE", "1000")) else 0.0) +
+                                   (2.0 if self.knobs.SLIDE_TAIL_OCC3 else 0.0) +
+                                   (4.0 if (Cp // 32) % 4 == 0 and Cp // 32 >= wide_from else 0.0) +
                                    (16.0 if self._is_fm(mo) else 0.0)),  # bit 4: u / mo fragment-major
                                 p=(u.data_ptr(), d[0].data_ptr(), mo.data_ptr(), d[1].data_ptr(), out.data_ptr(),
                                    d[2].data_ptr(), _dp(out_cm))),
@@ -1293,7 +1298,7 @@ class DenoiserEngine:
         rows = B * 16 * K
         ldg = ru(Cg)
         nsplit = 0
-        if self.prec == 1 and self.use_glds and os.environ.get("SLIDE_GATHER", "1") != "0":
+        if self.prec == 1 and self.use_glds and self.knobs.SLIDE_GATHER:
             nsplit = (C // 8) * 8 // 32
         c_begin = nsplit * 32
         g = self.A.zeros(rows, ldg - c_begin, dtype=self.adt)
@@ -1416,7 +1421,7 @@ class DenoiserEngine:
         per-timestep t-embedding table).  The samplers swap it in for the four per-point GEMM launches (diffusion.py); the plan itself
         keeps them (forward() of the engine, parity tests of the layers)."""
         sd, fr = self.sd, getattr(self, "_chain_front", None)
-        if fr is None or self.prec != 1 or os.environ.get("SLIDE_POINT_CHAIN", "1") == "0":
+        if fr is None or self.prec != 1 or not self.knobs.SLIDE_POINT_CHAIN:
             return None
         m2 = fr["m2"]
         ident = lambda c: gn_layout(c).identity and gn_layout(c).gs == 4
@@ -1453,7 +1458,7 @@ class DenoiserEngine:
         # round 6: the chain in the SPLIT arithmetic -- low fragments lo' = fp16((w - fp16(w)) 2^11) of the four
         # weight matrices.  These layers are the end of the network: their operand rounding reaches the prediction unattenuated
         # (tools/prec_select_feat.py), at 0.3 % of the FLOPs.  SLIDE_POINT_CHAIN_WIDE=0: fp16 operands as in round 5.
-        if os.environ.get("SLIDE_POINT_CHAIN_WIDE", "1") != "0":
+        if self.knobs.SLIDE_POINT_CHAIN_WIDE:
             def lo(w):
                 w = np.asarray(w, np.float32)
                 return ((w - w.astype(np.float16).astype(np.float32)) * np.float32(2048.0)).astype(np.float32)
@@ -1488,7 +1493,7 @@ class DenoiserEngine:
     def _build(self):
         hp, sd, B, A = self.hp, self.sd, self.B, self.A
         arch = hp["architecture"]
-        self.persistent = int(os.environ.get('SLIDE_PERSISTENT', '0'))  # 1: tile counter per XCD, 2: static tile lists
+        self.persistent = self.knobs.SLIDE_PERSISTENT  # 1: tile counter per XCD, 2: static tile lists
         # persistent I/O + per-step state
         self.x = A.zeros(B, 16, self.cx)
         self.ts = A.zeros(B)
@@ -1515,10 +1520,10 @@ class DenoiserEngine:
         # (opt-in, SLIDE_CM_TABLES=1: chunk-major second copies of the per-point tables the first layers gather from, written
         # by prep_points / the attention tails -- measured neutral, 298-301 shapes/s either way: the gathers hit the vector cache)
         feat0_cm = None
-        if self.use_cm and os.environ.get("SLIDE_CM_TABLES", "0") != "0":
+        if self.use_cm and self.knobs.SLIDE_CM_TABLES:
             feat0_cm = self._cm_copy[self.feat0.data_ptr()] = self._buf(B * 16, C0)
         # COPY launches folded into the producers of their sources (SLIDE_FOLD_COPIES=0: separate launches)
-        self.fold_copies = os.environ.get("SLIDE_FOLD_COPIES", "1") != "0"
+        self.fold_copies = self.knobs.SLIDE_FOLD_COPIES
         self._prep_copies, self._tail_of = [], {}  # _tail_of: output table (data_ptr) -> the fused tail / block body that writes it
         prep = self._emit(make_op(OP_PREP_POINTS, i=(B, self.cx, self.feat0.shape[1], self.prec),
                                   p=(self.x.data_ptr(), self.xyz.data_ptr(), self.feat0.data_ptr(), self.kidx.data_ptr(),
@@ -1531,7 +1536,7 @@ class DenoiserEngine:
         for i in range(nsa):
             j = i + nfp - nsa
             extra = ()
-            if 0 <= j < nfp and os.environ.get("SLIDE_MERGE_Q", "1") != "0":
+            if 0 <= j < nfp and self.knobs.SLIDE_MERGE_Q:
                 fp_q[j] = self._attention_query("FP_modules.%d.attention_module" % j, 8)
                 extra = (fp_q[j],)
             o, c = self._sa_module(i, feats[i], chans[i], extra_q=extra)
@@ -1659,7 +1664,7 @@ class DenoiserEngine:
         # merged and 371 with the chains of <= 256 KB of weights against 374 without: a chain's 20-odd workgroups each stream
         # ALL its weights (660 KB for the feature net's FP1.mlp2) and pay every layer's descriptor -> operands -> epilogue ->
         # store round trips in sequence, where the wide-grid launches of the other chains fill the same CUs meanwhile
-        max_kb = int(os.environ.get("SLIDE_GEMM_CHAIN", "0"))
+        max_kb = self.knobs.SLIDE_GEMM_CHAIN
         if self.prec != 1 or not self.use_glds or max_kb <= 0:
             return lambda plan, i: None
 
@@ -1687,7 +1692,7 @@ class DenoiserEngine:
         """the mode-1 (keys -> u) and mode-0 (first Mlp layer) generated-X GEMMs of an FP block are independent and adjacent in
         the plan: where both run 64-channel tiles at two workgroups per CU they become ONE SLIDE_OP_GEMM_GX_DUAL launch
         (SLIDE_GX_DUAL=0: two launches)."""
-        if os.environ.get("SLIDE_GX_DUAL", "1") == "0":
+        if not self.knobs.SLIDE_GX_DUAL:
             return lambda plan, i: None
 
         def match(plan, i):
@@ -1707,7 +1712,7 @@ class DenoiserEngine:
         """SA blocks: [per-point query GEMM P | keys -> u GEMM (needs P) | fused Mlp chain (needs neither)] becomes
         [chain + query GEMM in ONE launch (SLIDE_OP_SA_CHAIN_P) | keys -> u GEMM]: the query GEMM's launch and gap disappear under
         the chain (SLIDE_CHAIN_P=0: three launches)."""
-        if os.environ.get("SLIDE_CHAIN_P", "1") == "0":
+        if not self.knobs.SLIDE_CHAIN_P:
             return lambda plan, i: None
         is_p = lambda o: (o.kind == OP_GEMM and o.i[4] == 4 and o.i[6] == 1 and not (o.i[8] & 6) and o.i[9] != 3 and o.p[3] and o.p[6]
                           and not any(o.p[k] for k in (8, 9, 10, 11, 12, 13)))
@@ -1731,7 +1736,7 @@ class DenoiserEngine:
         # OPT-IN (SLIDE_PP=1): measured SLOWER -- one workgroup per sample re-reads every layer's weights per sample and its K loop is a
         # chain of dependent L2 round trips on four waves: 55 - 131 us per stage launch against 27 - 45 us for the launches it replaces
         # (position chain alone 365 -> 652 us per step, bench 379 -> 227 shapes/s)
-        if not self.use_gxs or os.environ.get("SLIDE_PP", "0") == "0":
+        if not self.use_gxs or not self.knobs.SLIDE_PP:
             return lambda plan, i: None
         B = self.B
 

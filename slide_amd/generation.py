@@ -15,6 +15,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import knobs
 from .configs import CATEGORY_IDS, CATEGORY_NAMES
 
 
@@ -22,7 +23,7 @@ def init_distributed():
     """(rank, world, device, gather_device) of this process.  One process per GPU over RCCL (backend "nccl", bound to the rank's
     GPU); SLIDE_SHARE_GPU=1 (test knob for 1-GPU boxes): every rank uses device 0 and the collectives run on gloo / CPU tensors."""
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
-    share = os.environ.get("SLIDE_SHARE_GPU", "0") != "0"
+    share = knobs.read("SLIDE_SHARE_GPU")
     if share:
         local = 0
     torch.cuda.set_device(local)
@@ -329,7 +330,7 @@ class PipelinedGenerator:
         # dependent launches beside the feature chains; SLIDE_POS_MULT=1 keeps one batch per chain).  The chains' per-sample arithmetic
         # and noise streams do not depend on the batch they run in.
         wide = (pos is not None and feat is not None and not serial and resolve_prec(prec)[0] != "fp16" and resolve_prec(prec)[1] == "fp16")
-        self.pos_mult = 2 if (wide and int(os.environ.get("SLIDE_POS_MULT", "2")) == 2) else 1
+        self.pos_mult = 2 if (wide and knobs.read("SLIDE_POS_MULT") == 2) else 1
         self._pos2 = None
         if self.pos_mult == 2:
             # (built BEFORE the feature samplers, and the one-batch position sampler runs on ITS stream: the runtime maps streams onto the

@@ -3,15 +3,13 @@
 (the parity mode every module-level test uses).  `SLIDE_MODULE_PREC=fp16` switches the GEMM operands (weights, the
 transposed activation copy) to fp16 with fp32 accumulation and fp32 outputs -- the throughput mode of the encode / decode
 paths.  Inference only.  The fused, layout-optimised path for the DDPM configs is slide_amd.engine.DenoiserEngine."""
-import os
-
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .abi import EPI_RAW, F_OUT_F32, OP_GROUPNORM_NCHW, OP_TRANSPOSE, SlideEpi, make_op, ru
 from .abi import run_op as _run
-from .rows import module_gemm_op
+from .rows import half_mode, module_gemm_op
 
 
 class _GemmPlan:
@@ -21,7 +19,7 @@ class _GemmPlan:
         O, I = weight.shape[0], int(np.prod(weight.shape[1:]))
         self.O, self.I, self.rows = O, I, rows
         self.kp, self.op_ = ru(I), ru(O)
-        self.half = os.environ.get("SLIDE_MODULE_PREC", "fp32") == "fp16"
+        self.half = half_mode()
         adt = torch.float16 if self.half else torch.float32
         W = torch.zeros(self.op_, self.kp, device=device, dtype=torch.float32)
         W[:O, :I] = weight.detach().reshape(O, I).float()

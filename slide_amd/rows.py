@@ -9,8 +9,6 @@ the t- and class-embedding adds / the residual run in place in one pass, and the
 Reference-layout tensors exist only at module boundaries (`from_ncx` / `to_ncx`).
 
 Everything here launches kernels of libslide_hip.so (rows_ops.hip + the engine GEMM); there is no CPU fallback."""
-import os
-
 import numpy as np
 import torch
 
@@ -20,10 +18,11 @@ from .abi import (EPI_RAW, EPI_STATS, F_OUT_F32, F_PRE_RELU, GN_APPLY_ONLY, GN_P
                   OP_ROWS_PAIR_EXPAND, OP_ROWS_POOL, OP_ROWS_TO_NCX, POOL_AVG, POOL_MAX, POOL_MAX_AVG, SlideEpi, SlideOp,
                   make_op, ru)
 from .abi import run_op as _run
+from . import knobs
 
 
 def half_mode():
-    return os.environ.get("SLIDE_MODULE_PREC", "fp32") == "fp16"
+    return knobs.read("SLIDE_MODULE_PREC") == "fp16"
 
 
 def _rop(kind, half, i, p):
@@ -172,7 +171,7 @@ class _PinnedUploader:
 
     def upload(self, arr, device):
         n = arr.nbytes
-        if n > self.SLOT or os.environ.get("SLIDE_PINNED_TABLES", "1") == "0":
+        if n > self.SLOT or not knobs.read("SLIDE_PINNED_TABLES"):
             return torch.from_numpy(arr.copy()).to(device)
         if self.buf is None:
             self.buf = torch.empty(self.SLOT * self.NSLOT, dtype=torch.uint8).pin_memory()
@@ -199,7 +198,7 @@ def module_gemm_op(rows, kp, n_cob, half, in_bs=0, f=(), p=()):
     fp32 or (half) fp16 operands on the LDS-DMA ring kernels; four-block column tiles only on request (SLIDE_MODULE_CBW4) and when
     they still give 256 workgroups"""
     ntr = (rows + 255) // 256
-    cbw = 4 if (half and n_cob >= 4 and ntr * ((n_cob + 3) // 4) >= 256 and os.environ.get("SLIDE_MODULE_CBW4", "0") != "0") else 2
+    cbw = 4 if (half and n_cob >= 4 and ntr * ((n_cob + 3) // 4) >= 256 and knobs.read("SLIDE_MODULE_CBW4")) else 2
     return make_op(OP_GEMM, i=(rows, kp, kp, n_cob, 8, in_bs, int(half), cbw, int(half), 0), f=f, p=p)
 
 
@@ -222,7 +221,7 @@ class _ConvPlan:
         pv = np.zeros((self.op_ // 32, 3, 32), np.float32)
         pv[:, 0, :] = self.vec.cpu().numpy().reshape(-1, 32)
         self._pv = pv.reshape(-1).view(np.uint8)
-        self._tag = 1 if os.environ.get("SLIDE_PACKED_VECS", "1") != "0" else 0
+        self._tag = int(knobs.read("SLIDE_PACKED_VECS"))
 
     def epi(self, out, stats=None, pre_relu=False, pre_add=None, out_f32=False):
         """pre_add = (per-point tensor [points][ld], log2 K): + pre_add[row >> log2 K] before the ReLU (SlideEpi.pre_add)"""
@@ -307,11 +306,11 @@ def sample_sums(v):
 
 
 def fused_stats():
-    return os.environ.get("SLIDE_MODULE_STATS", "1") != "0"
+    return knobs.read("SLIDE_MODULE_STATS")
 
 
 def deferral():
-    return half_mode() and os.environ.get("SLIDE_MODULE_DEFER", "1") != "0"
+    return half_mode() and knobs.read("SLIDE_MODULE_DEFER")
 
 
 def materialise(x):
@@ -441,7 +440,7 @@ def group(xyz, new_xyz, feat, idx, flags, d2=None, empty_counts=None, half=None)
     spec = (xyz.contiguous().float(), new_xyz.contiguous().float(), feat, idx, flags, d2.contiguous() if d2 is not None else None,
             empty_counts, half)
     if (half and empty_counts is None and not (flags & GROUP_NO_XYZ) and B * npnt * K > 0 and ru(C + ncoord) <= 1024
-            and os.environ.get("SLIDE_MODULE_PAIR", "1") != "0"):
+            and knobs.read("SLIDE_MODULE_PAIR")):
         return LazyGroup(spec, B, npnt * K, C + ncoord, ru(C + ncoord), half)
     return Rows(_group_now(*spec), B, npnt * K, C + ncoord)
 
@@ -568,7 +567,7 @@ def conv_attend(u, module, values, K, counts=None):
     convolution's 256 x 64 output tile is soft-maxed over the neighbour rows and contracted with the value rows in the GEMM's epilogue.
     fp16 rows, K in (4, 8, 16, 32), tiles that do not straddle samples; otherwise (or SLIDE_MODULE_FUSE_ATTEND=0) the two launches."""
     ok = (u.half and K in (4, 8, 16, 32) and u.rows % 256 == 0 and u.rows == values.rows and u.rows > 0 and
-          os.environ.get("SLIDE_MODULE_FUSE_ATTEND", "1") != "0" and (u.pending is None or u.S % 256 == 0) and u.ld <= 1536)
+          knobs.read("SLIDE_MODULE_FUSE_ATTEND") and (u.pending is None or u.S % 256 == 0) and u.ld <= 1536)
     if not ok:
         return attend(conv(u, module), values, K, counts)
     w, bias = module.weight, module.bias
