@@ -19,6 +19,8 @@
  *
  * Part 4 is the Chamfer / F1 metric (the reference's pointnet2/metrics_point_cloud/chamfer_and_f1.py, forward only).
  *
+ * Part 5 is DPSR, oriented points to the Poisson indicator grid (the reference's pointnet2/dpsr_utils/dpsr.py, forward only).
+ *
  * Part 3 is the fused latent-DDPM denoiser engine (the reference runs these as ~80 torch module
  * launches per step: pointnet2/models/pointnet2_with_pcld_condition.py:286-489).
  */
@@ -138,6 +140,46 @@ SLIDE_API int slide_emd_pairwise(int m, int n, int p, int q, const float *x, int
  * pointer other than cells; 0 without a launch when s or p is 0. */
 SLIDE_API int slide_occupancy_grid(int s, int p, const float *pts, int sp, int r, const float *axis, const uint32_t *rowmask,
                                    int *counts, int *clouds, int *cells, int *flag, slide_stream_t stream);
+
+/* ------------------------------------------------------------------ Part 5: DPSR, oriented points -> Poisson indicator grid */
+/* The forward of the reference's pointnet2/dpsr_utils/dpsr.py (DPSR.forward) in separately callable launches; the arithmetic of
+ * every step is written out in csrc/dpsr.hip.  Grids are cubic, r cells per axis, flat index (i r + j) r + k; complex arrays are
+ * interleaved (re, im) floats; h = r / 2 + 1.  The FFT entry points take r in {16, 32, 64, 128, 256} (-2 otherwise); every entry
+ * point returns -2 for a NULL array or an argument out of range and 0 without a launch for an empty batch.
+ *
+ * Trilinear scatter.  pts (b,n,3) f32 coordinates in [0, 1), vals (b,n,nf) f32, nf 1 or 3 -> grid (b,nf,r,r,r) int64, ACCUMULATED
+ * into (the caller zero-fills): every point adds llrint(fl(w_c * v) * 2^32) to the 8 corners of its cell (periodic wrap of the last
+ * cell) with integer atomics -- exact, independent of order and batch.  flag (1) int32 |= 1 when a point was left out: a non-finite
+ * coordinate or value, a coordinate outside [0, 1), |v| >= 2^20.  2 <= r <= 1024. */
+SLIDE_API int slide_point_rasterize(int b, int n, int nf, int r, const float *pts, const float *vals, long long *grid, int *flag,
+                                    slide_stream_t stream);
+/* out[i] = fl(fl(grid[i]) * 2^-32): the fixed-point grid as floats (what slide_fft3_r2c reads with fixed_point = 1) */
+SLIDE_API int slide_grid_fixed_to_float(long long count, const long long *grid, float *out, slide_stream_t stream);
+/* Trilinear gather (the reference's grid_interp).  grid (b,r,r,r,c) f32, pts (b,n,3) in [0, 1) -> out (b,n,c), the 8 corners summed
+ * in corner order; same cell arithmetic and wrap as the scatter.  flag |= 1 for a coordinate outside [0, 1) (its outputs are 0). */
+SLIDE_API int slide_grid_interp(int b, int n, int c, int r, const float *grid, const float *pts, float *out, int *flag,
+                                slide_stream_t stream);
+/* 3-D real FFT of nb grids (numpy's rfftn over the three grid axes): in (nb,r,r,r), f32 or with fixed_point != 0 the int64 grid of
+ * slide_point_rasterize (read times 2^-32) -> spec (nb,r,r,h) complex.  Three launches: axis 3, then axes 2 and 1 in place. */
+SLIDE_API int slide_fft3_r2c(int nb, int r, const void *in, int fixed_point, float *spec, slide_stream_t stream);
+/* Its inverse (numpy's irfftn(s = (r,r,r))): spec (nb,r,r,h) complex, OVERWRITTEN (axes 1 and 2 are transformed in place) -> out
+ * (nb,r,r,r) f32.  The last launch extends every axis-3 line Hermitian-symmetrically, dropping the imaginary part of bins 0 and
+ * r/2, and scales by 1 / r^3. */
+SLIDE_API int slide_fft3_c2r(int nb, int r, float *spec, float *out, slide_stream_t stream);
+/* The spectral Poisson solve: spec (b,3,r,r,h) complex, g (r,r,h) f32 (the module's Gaussian filter) -> phis (b,r,r,h) complex,
+ * sum_d(-i omega_d g spec_d) / (-|omega|^2 + 1e-6) with omega_d = fl(k_d * fl(2 pi)) and bin (0,0,0) = 0. */
+SLIDE_API int slide_dpsr_spectral(int b, int r, const float *spec, const float *g, float *phis, slide_stream_t stream);
+/* Shift and scale in place: offset = mean_n fv (b,n) when shift (a fixed-order sum, no atomics), else 0; phi (b,r,r,r) -= offset; then
+ * with a = |phi[.,0,0,0]| read AFTER the shift, phi = -phi / a * 0.5 when scale.  coef (b,2) f32 receives (offset, a).  Two launches;
+ * none when neither flag is set. */
+SLIDE_API int slide_dpsr_finish(int b, int n, int r, const float *fv, int shift, int scale, float *coef, float *phi,
+                                slide_stream_t stream);
+/* All of it for b samples: pts / normals (b,n,3), g (r,r,h) -> phi (b,r,r,r).  Workspaces of the caller: ws_grid (b,3,r,r,r) int64
+ * (zero-filled here), ws_spec (b,3,r,r,h) complex, ws_phis (b,r,r,h) complex, ws_fv (b,n) f32, ws_coef (b,2) f32; flag as above
+ * (the caller zero-fills).  A sample's result does not depend on b or on its position. */
+SLIDE_API int slide_dpsr_grid(int b, int n, int r, const float *pts, const float *normals, const float *g, int shift, int scale,
+                              long long *ws_grid, float *ws_spec, float *ws_phis, float *ws_fv, float *ws_coef, float *phi, int *flag,
+                              slide_stream_t stream);
 
 /* ------------------------------------------------------------------ Part 3: denoiser engine */
 /* see slide_engine.h */

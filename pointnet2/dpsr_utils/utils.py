@@ -1,0 +1,48 @@
+"""The DPSR helpers of the reference's pointnet2/dpsr_utils/utils.py (lines 24-196) on the HIP kernels of slide_amd/csrc/dpsr.hip:
+same names, arguments and return shapes; 3-D cubic grids, CUDA float tensors, forward only.
+
+  fftfreqs, spec_gaussian_filter   host tensors, the reference's values bit for bit (numpy's fftfreq / rfftfreq; the filter in float64)
+  point_rasterize(pts, vals, size) trilinear scatter, (B, nf, r, r, r) float: converted once per cell from the kernel's exact
+                                   64-bit fixed-point sums (bit-reproducible, unlike a float scatter_add_)
+  grid_interp(grid, pts, batched)  trilinear gather, (B, n, C)
+"""
+import numpy as np
+import torch
+
+from slide_amd import _ext as _hip
+
+
+def fftfreqs(res, dtype=torch.float32, exact=True):
+    """frequency tensor (*res[:-1], res[-1] / 2 + 1, len(res)): fftfreq on every axis but the last, rfftfreq on the last (without its
+    Nyquist bin when not exact)"""
+    freqs = [torch.tensor(np.fft.fftfreq(r, d=1 / r), dtype=dtype) for r in res[:-1]]
+    last = np.fft.rfftfreq(res[-1], d=1 / res[-1])
+    freqs.append(torch.tensor(last if exact else last[:-1], dtype=dtype))
+    return torch.stack(torch.meshgrid(*freqs, indexing="ij"), dim=-1)
+
+
+def spec_gaussian_filter(res, sig):
+    """exp(-0.5 (2 sig |k| / res[0])^2) in float64, (*half spectrum shape, 1, 1)"""
+    omega = fftfreqs(res, dtype=torch.float64)
+    dis = torch.sqrt(torch.sum(omega ** 2, dim=-1))
+    return torch.exp(-0.5 * ((sig * 2 * dis / res[0]) ** 2)).unsqueeze(-1).unsqueeze(-1)
+
+
+def cubic_size(size):
+    """r of a 3-D cubic size tuple (the kernels' scope); ValueError otherwise"""
+    size = tuple(int(s) for s in size)
+    if len(size) != 3 or size[0] != size[1] or size[0] != size[2]:
+        raise ValueError("3-D cubic grids only, got size %s" % (size,))
+    return size[0]
+
+
+def point_rasterize(pts, vals, size):
+    """pts (B, n, 3) in [0, 1), vals (B, n, nf) with nf 1 or 3 -> (B, nf, *size)"""
+    return _hip.point_rasterize(pts, vals, cubic_size(size))
+
+
+def grid_interp(grid, pts, batched=True):
+    """grid (B, r, r, r, C), pts (B, n, 3) in [0, 1) -> (B, n, C); without `batched` both lack the leading axis"""
+    if not batched:
+        return _hip.grid_interp(grid.unsqueeze(0), pts.unsqueeze(0)).squeeze(0)
+    return _hip.grid_interp(grid, pts)

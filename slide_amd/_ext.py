@@ -420,3 +420,176 @@ def occupancy_grid(points, axis, mask, return_cells=False):
         if f & 2:
             raise ValueError("occupancy_grid: the mask admits no cell")
     return (counts, clouds, cells) if return_cells else (counts, clouds)
+
+
+# ---------------------------------------------------------------------------------------------------------------- DPSR
+FFT_SIZES = (16, 32, 64, 128, 256)
+_DPSR_WORKSPACE_BYTES = 1 << 30  # dpsr_grid's default chunk: as many samples as keep its workspace within this
+
+
+def _chk_f32_cuda(x, name, dim=None):
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("%s must be a CUDA tensor" % name)
+    _chk_float(x, name)
+    if dim is not None and x.dim() != dim:
+        raise RuntimeError("%s must have %d dimensions" % (name, dim))
+    return x.contiguous()
+
+
+def _chk_fft_size(r):
+    if r not in FFT_SIZES:
+        raise ValueError("the grid resolution must be one of %s, got %r" % (FFT_SIZES, r))
+
+
+def _raise_dpsr_flag(flag, what):
+    if int(flag.item()) & 1:
+        raise ValueError("%s: a coordinate is non-finite or outside [0, 1), or a value is non-finite or not below 2^20" % what)
+
+
+def _pts_vals(pts, vals, what):
+    pts = _chk_f32_cuda(pts, "pts", 3)
+    vals = _chk_f32_cuda(vals, "vals", 3)
+    if pts.size(2) != 3 or pts.shape[:2] != vals.shape[:2]:
+        raise ValueError("%s: pts (B,n,3) and vals (B,n,nf) must agree, got %s and %s" % (what, tuple(pts.shape), tuple(vals.shape)))
+    return pts, vals
+
+
+def point_rasterize_fixed(pts, vals, r):
+    """the trilinear scatter in 64-bit fixed point (include/slide_hip.h slide_point_rasterize): pts (B,n,3) in [0, 1), vals (B,n,nf),
+    nf 1 or 3 -> (B,nf,r,r,r) int64 in units of 2^-32.  Bit-reproducible; ValueError for a point the kernel left out."""
+    pts, vals = _pts_vals(pts, vals, "point_rasterize")
+    B, n, nf = vals.shape
+    if nf not in (1, 3):
+        raise ValueError("point_rasterize: 1 or 3 value columns, got %d" % nf)
+    grid = torch.zeros((B, nf, r, r, r), device=pts.device, dtype=torch.int64)
+    flag = torch.zeros(1, device=pts.device, dtype=torch.int32)
+    check(lib().slide_point_rasterize(B, n, nf, r, ptr(pts), ptr(vals), ptr(grid), ptr(flag), stream_of()), "point_rasterize")
+    if B and n:
+        _raise_dpsr_flag(flag, "point_rasterize")
+    return grid
+
+
+def grid_fixed_to_float(grid):
+    out = torch.empty(grid.shape, device=grid.device, dtype=torch.float32)
+    check(lib().slide_grid_fixed_to_float(grid.numel(), ptr(grid), ptr(out), stream_of()), "grid_fixed_to_float")
+    return out
+
+
+def point_rasterize(pts, vals, r):
+    """point_rasterize_fixed as floats: (B,nf,r,r,r) f32, each cell rounded once from the exact fixed-point sum"""
+    return grid_fixed_to_float(point_rasterize_fixed(pts, vals, r))
+
+
+def grid_interp(grid, pts):
+    """trilinear gather (slide_grid_interp): grid (B,r,r,r,C) f32, pts (B,n,3) in [0, 1) -> (B,n,C)"""
+    grid = _chk_f32_cuda(grid, "grid", 5)
+    pts = _chk_f32_cuda(pts, "pts", 3)
+    B, r, C = grid.size(0), grid.size(1), grid.size(4)
+    if grid.size(2) != r or grid.size(3) != r or pts.size(0) != B or pts.size(2) != 3 or C < 1:
+        raise ValueError("grid_interp: grid (B,r,r,r,C) and pts (B,n,3) expected, got %s and %s" % (tuple(grid.shape), tuple(pts.shape)))
+    out = torch.empty((B, pts.size(1), C), device=grid.device, dtype=torch.float32)
+    flag = torch.zeros(1, device=grid.device, dtype=torch.int32)
+    check(lib().slide_grid_interp(B, pts.size(1), C, r, ptr(grid), ptr(pts), ptr(out), ptr(flag), stream_of()), "grid_interp")
+    if B and pts.size(1):
+        _raise_dpsr_flag(flag, "grid_interp")
+    return out
+
+
+def fft3_r2c(x):
+    """numpy's rfftn over the last three axes: x (..., r, r, r) f32, or the int64 grid of point_rasterize_fixed (read times 2^-32)
+    -> (..., r, r, r/2 + 1) complex64"""
+    if not x.is_cuda or x.dtype not in (torch.float32, torch.int64) or x.dim() < 3:
+        raise RuntimeError("fft3_r2c: a CUDA float or int64 tensor of at least three dimensions is expected")
+    r = x.size(-1)
+    _chk_fft_size(r)
+    if x.size(-2) != r or x.size(-3) != r:
+        raise ValueError("fft3_r2c: cubic grids only, got %s" % (tuple(x.shape),))
+    x = x.contiguous()
+    spec = torch.empty(tuple(x.shape[:-1]) + (r // 2 + 1, 2), device=x.device, dtype=torch.float32)
+    check(lib().slide_fft3_r2c(x.numel() // r ** 3, r, ptr(x), int(x.dtype == torch.int64), ptr(spec), stream_of()), "fft3_r2c")
+    return torch.view_as_complex(spec)
+
+
+def fft3_c2r(spec, overwrite=False):
+    """numpy's irfftn(s = (r, r, r)) over the last three axes: spec (..., r, r, r/2 + 1) complex64 -> (..., r, r, r) f32.  The
+    kernels transform axes 1 and 2 in place: overwrite=False works on a copy."""
+    if not spec.is_cuda or spec.dtype != torch.complex64 or spec.dim() < 3:
+        raise RuntimeError("fft3_c2r: a CUDA complex64 tensor of at least three dimensions is expected")
+    r = spec.size(-2)
+    _chk_fft_size(r)
+    if spec.size(-3) != r or spec.size(-1) != r // 2 + 1:
+        raise ValueError("fft3_c2r: (..., r, r, r/2 + 1) expected, got %s" % (tuple(spec.shape),))
+    work = torch.view_as_real(spec.contiguous() if overwrite else spec.clone(memory_format=torch.contiguous_format))
+    out = torch.empty(tuple(spec.shape[:-1]) + (r,), device=spec.device, dtype=torch.float32)
+    check(lib().slide_fft3_c2r(out.numel() // r ** 3, r, ptr(work), ptr(out), stream_of()), "fft3_c2r")
+    return out
+
+
+def dpsr_spectral(spec, G):
+    """the spectral Poisson solve (slide_dpsr_spectral): spec (B,3,r,r,h) complex64, G r*r*h f32 -> (B,r,r,h) complex64"""
+    if not spec.is_cuda or spec.dtype != torch.complex64 or spec.dim() != 5 or spec.size(1) != 3:
+        raise RuntimeError("dpsr_spectral: a CUDA complex64 tensor (B,3,r,r,h) is expected")
+    B, r = spec.size(0), spec.size(2)
+    _chk_fft_size(r)
+    G = _chk_f32_cuda(G, "G")
+    if G.numel() != r * r * (r // 2 + 1) or tuple(spec.shape[2:]) != (r, r, r // 2 + 1):
+        raise ValueError("dpsr_spectral: spec (B,3,r,r,r/2+1) and G of r*r*(r/2+1) values expected")
+    s = torch.view_as_real(spec.contiguous())
+    out = torch.empty((B, r, r, r // 2 + 1, 2), device=spec.device, dtype=torch.float32)
+    check(lib().slide_dpsr_spectral(B, r, ptr(s), ptr(G), ptr(out), stream_of()), "dpsr_spectral")
+    return torch.view_as_complex(out)
+
+
+def dpsr_finish(phi, fv, shift=True, scale=True):
+    """shift and scale IN PLACE (slide_dpsr_finish): phi (B,r,r,r) f32, fv (B,n) f32 -> phi"""
+    phi = _chk_f32_cuda(phi, "phi", 4)
+    fv = _chk_f32_cuda(fv, "fv", 2)
+    B, r = phi.size(0), phi.size(1)
+    coef = torch.empty((B, 2), device=phi.device, dtype=torch.float32)
+    check(lib().slide_dpsr_finish(B, fv.size(1), r, ptr(fv), int(shift), int(scale), ptr(coef), ptr(phi), stream_of()), "dpsr_finish")
+    return phi
+
+
+def dpsr_chunk(r, n, chunk=None):
+    """samples per slide_dpsr_grid call: the workspace (int64 grid + half spectra, about 84 MB per sample at r 128) stays bounded"""
+    if chunk is not None:
+        if int(chunk) < 1:
+            raise ValueError("chunk must be positive")
+        return int(chunk)
+    h = r // 2 + 1
+    per = 3 * r ** 3 * 8 + 4 * r * r * h * 8 + 4 * n + 8
+    return max(1, _DPSR_WORKSPACE_BYTES // per)
+
+
+def dpsr_grid(pts, normals, G, shift=True, scale=True, chunk=None):
+    """DPSR.forward on the composed entry point (slide_dpsr_grid): pts / normals (B,n,3) f32, G the filter of r*r*(r/2+1) floats of
+    shape (r,r,r/2+1,...) -> phi (B,r,r,r) f32.  Samples run `chunk` at a time (default: dpsr_chunk); a sample's grid does not depend
+    on the chunk or the batch.  One host read of a flag word at the end: ValueError for a point the kernels rejected."""
+    pts, normals = _pts_vals(pts, normals, "dpsr_grid")
+    if normals.size(2) != 3 or pts.size(1) < 1:
+        raise ValueError("dpsr_grid: normals (B,n,3) with n >= 1 expected, got %s" % (tuple(normals.shape),))
+    G = _chk_f32_cuda(G, "G")
+    r = G.size(0)
+    _chk_fft_size(r)
+    h = r // 2 + 1
+    if G.numel() != r * r * h:
+        raise ValueError("dpsr_grid: G must hold r*r*(r/2+1) values")
+    B, n = pts.size(0), pts.size(1)
+    dev = pts.device
+    phi = torch.empty((B, r, r, r), device=dev, dtype=torch.float32)
+    if B == 0:
+        return phi
+    cb = min(dpsr_chunk(r, n, chunk), B)
+    ws_grid = torch.empty((cb, 3, r, r, r), device=dev, dtype=torch.int64)
+    ws_spec = torch.empty((cb, 3, r, r, h, 2), device=dev, dtype=torch.float32)
+    ws_phis = torch.empty((cb, r, r, h, 2), device=dev, dtype=torch.float32)
+    ws_fv = torch.empty((cb, n), device=dev, dtype=torch.float32)
+    ws_coef = torch.empty((cb, 2), device=dev, dtype=torch.float32)
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    for s in range(0, B, cb):
+        e = min(s + cb, B)
+        check(lib().slide_dpsr_grid(e - s, n, r, ptr(pts[s:e]), ptr(normals[s:e]), ptr(G), int(shift), int(scale), ptr(ws_grid),
+                                    ptr(ws_spec), ptr(ws_phis), ptr(ws_fv), ptr(ws_coef), ptr(phi[s:e]), ptr(flag), stream_of()),
+              "dpsr_grid")
+    _raise_dpsr_flag(flag, "dpsr_grid")
+    return phi

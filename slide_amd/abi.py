@@ -171,6 +171,14 @@ PROTOTYPES = {name: _proto(args) for name, args in {
     "slide_chamfer_pairwise": "iiiipipiipp",
     "slide_emd_pairwise": "iiiipipiipp",
     "slide_occupancy_grid": "iipiippppppp",
+    "slide_point_rasterize": "iiiippppp",
+    "slide_grid_fixed_to_float": "qppp",
+    "slide_grid_interp": "iiiippppp",
+    "slide_fft3_r2c": "iipipp",
+    "slide_fft3_c2r": "iippp",
+    "slide_dpsr_spectral": "iipppp",
+    "slide_dpsr_finish": "iiipiippp",
+    "slide_dpsr_grid": "iiipppiipppppppp",
     "slide_hip_device_ok": "",
     "slide_lane_reduce_selftest": "pppip",
     # include/slide_engine.h
