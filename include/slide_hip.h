@@ -193,6 +193,13 @@ SLIDE_API int slide_hip_device_ok(void); /* 1 if a gfx950 device is visible */
  * Returns -2 for another nv or a NULL pointer. */
 SLIDE_API int slide_lane_reduce_selftest(const float *in, float *out_new, float *out_old, int nv, slide_stream_t stream);
 
+/* Self-test of the noise the DDPM update kernels draw in registers (csrc/ddpm_update.h philox_normal: Philox4x32-10 keyed with the
+ * seed on the counter (element, step, 0x243F6A88 ^ nonce, 0x85A308D3), Box-Muller on the first two output words):
+ * out[i] = philox_normal(seed, step, elem0 + i, nonce) for i < n (element numbers wrap at 2^32).  seed_lo .. elem0 carry the bit
+ * patterns of 32-bit unsigned words.  Returns -2 for n < 0 or a NULL out with n > 0; n == 0 launches nothing. */
+SLIDE_API int slide_philox_normal_selftest(int seed_lo, int seed_hi, int step, int nonce, int elem0, int n, float *out,
+                                           slide_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

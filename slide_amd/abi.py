@@ -181,6 +181,7 @@ PROTOTYPES = {name: _proto(args) for name, args in {
     "slide_dpsr_grid": "iiipppiipppppppp",
     "slide_hip_device_ok": "",
     "slide_lane_reduce_selftest": "pppip",
+    "slide_philox_normal_selftest": "iiiiiipp",
     # include/slide_engine.h
     "slide_run_ops": "pip",
     "slide_run_ops2": "pipp",

@@ -22,13 +22,17 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # GEMM sources: the epilogue's per-channel-block loop must unroll fully (the accumulators are indexed by it; left rolled
 # they are demoted to scratch), which needs more than LLVM's default 16k-instruction cap for `#pragma unroll`.
 UNROLL = ["-mllvm", "-pragma-unroll-threshold=100000"]
+# engine.hip: the DDPM update kernels draw their timestep ticket (ddpm_update.h) with a returning atomic whose result is first
+# needed after their last store.  LLVM's atomic optimizer would rewrite that one-lane atomic into ballot + atomic + readfirstlane,
+# and the readfirstlane waits for the atomic where it is issued; the file has no other atomics.
+NO_ATOMIC_OPT = ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]
 SOURCES = [("point_ops.hip", ["-ffp-contract=off"]), ("chamfer.hip", ["-ffp-contract=off"]),
            ("chamfer_pairwise.hip", ["-ffp-contract=off"]), ("chamfer_bwd.hip", ["-ffp-contract=off"]),
            ("occupancy_grid.hip", ["-ffp-contract=off"]), ("emd_pairwise.hip", ["-ffp-contract=off"]),
-           ("dpsr.hip", ["-ffp-contract=off"]), ("engine.hip", UNROLL), ("gemm_ring.hip", UNROLL), ("attn_tail.hip", UNROLL),
+           ("dpsr.hip", ["-ffp-contract=off"]), ("engine.hip", UNROLL + NO_ATOMIC_OPT), ("gemm_ring.hip", UNROLL), ("attn_tail.hip", UNROLL),
            ("gemm_gx.hip", UNROLL), ("gemm_gxs.hip", UNROLL),
            ("point_chain.hip", UNROLL), ("rows_ops.hip", []), ("train_ops.hip", []), ("encoder_ops.hip", []),
-           ("group_coord_bwd.hip", ["-ffp-contract=off"]), ("lane_reduce_selftest.hip", [])]
+           ("group_coord_bwd.hip", ["-ffp-contract=off"]), ("lane_reduce_selftest.hip", []), ("philox_selftest.hip", [])]
 SOURCES_EXP = SOURCES + [("experiments/block_body.hip", UNROLL), ("experiments/gemm_xs.hip", UNROLL), ("experiments/gemm_chain.hip", UNROLL),
                          ("experiments/resident.hip", UNROLL)]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",

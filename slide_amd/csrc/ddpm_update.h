@@ -29,8 +29,46 @@ __device__ __forceinline__ float philox_normal(uint32_t seed_lo, uint32_t seed_h
   return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
 }
 
-// The update kernel also advances the device-side timestep: every block read t / step at its start, so the block that
-// finishes LAST (a counter in t_dev[2]) may write t - 1 / step + 1 for the next replay -- one launch less per step.
+// The update launch also advances the device-side timestep (one launch less per step): t_dev[2] counts workgroups, and the
+// workgroup that finds itself last writes t - 1 / step + 1 for the next launch and puts the counter back to 0.
+//
+// Two forms.  advance_t_last_block counts the workgroups that have FINISHED, behind a device-scope fence; the launches that
+// carry an update in their epilogue (point_chain.hip, head_update_kernel, experiments/resident.hip) use it.  The update kernels
+// themselves use the ticket form below, which has no fence, no release and no acquire, on this invariant:
+//
+//   * Nothing is handed between workgroups inside the launch.  Every workgroup reads t_dev[0] / [1] / [3] / [4] as the
+//     PREVIOUS launch left them and writes only its own elements of the state; x, feat0 and the new t_dev reach the next
+//     launch through the kernel boundary, which orders all of a launch's stores before the next launch's loads.
+//   * The one thing a workgroup must know before t_dev[0] is overwritten is that every workgroup has already READ it.  A
+//     workgroup knows that about itself as soon as the values are in its registers, so it draws its ticket THEN
+//     (t_ticket_draw: after a waited load and a workgroup barrier, i.e. when every wave of the workgroup holds t and step),
+//     not when it finishes.  The relaxed fetch-add is issued early and its return is first needed after the workgroup's last
+//     store (t_ticket_settle), so its latency hides under the arithmetic.
+//   * The workgroup whose ticket is total - 1 drew last: all other workgroups drew before it, hence hold t already.  Only
+//     it writes t - 1, so NO reader of this launch can see t - 1; the three writes are plain stores and need no order
+//     among themselves, because nobody reads them before the launch ends.
+//
+// A caller of the ticket form must make the values ARRIVE before the draw -- requesting them is not enough, and a barrier
+// does not wait for outstanding loads: t_hold() below is the wait.  The update kernels also wait there for the element loads they
+// issued with the t_dev read (arrived()): the loads share that one round trip, and with nothing else outstanding when the ticket
+// is drawn no later wait of the wave (loads return in order) can stall on the ticket before the stores are out.
+__device__ __forceinline__ void t_hold(int t, int step) {  // the wave's t / step loads have returned when this has executed
+  asm volatile("" ::"s"(t), "s"(step) : "memory");
+}
+__device__ __forceinline__ void arrived(float v) {  // the same for a per-lane value
+  asm volatile("" ::"v"(v) : "memory");
+}
+__device__ __forceinline__ int t_ticket_draw(int *t_dev) {  // ONE thread per workgroup, after t_hold() + __syncthreads()
+  return __hip_atomic_fetch_add(&t_dev[2], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void t_ticket_settle(int *t_dev, int ticket, int total, int t, int step) {  // the same thread
+  if (ticket == total - 1) {
+    t_dev[2] = 0;
+    t_dev[0] = t - 1;
+    t_dev[1] = step + 1;
+  }
+}
+
 __device__ __forceinline__ void advance_t_last_block(int *t_dev, int t, int step) {
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -315,6 +315,10 @@ __global__ __launch_bounds__(256) void cond_kernel(int dim, int n_out, const int
 
 // ------------------------------------------------------------------------------------------------ DDPM updates
 // (Philox noise, timestep advance, update_feat_element: ddpm_update.h)
+// Both kernels hand the timestep over with the ticket form of ddpm_update.h and are laid out around ONE exposed round trip, the read
+// of t_dev: the state, the prediction and the condition do not depend on t and are requested with it; the coefficients (scalar
+// loads indexed by t) are requested behind the barrier and arrive under the Philox / Box-Muller draw, which needs only step, the
+// nonce and the element number.  The arithmetic, operation by operation, is update_feat_element's (ddpm_update.h).
 // sampling() update (pointnet2/util.py:247-253): x = (x - c_eps[t]*eps)/sqrt_alpha[t]; t>0: x += sigma[t]*z
 __global__ __launch_bounds__(256) void update_pos_kernel(int n, int eps_ld, uint32_t seed_lo, uint32_t seed_hi, float *__restrict__ x,
                                                          const float *__restrict__ eps, const float *__restrict__ noise,
@@ -323,22 +327,59 @@ __global__ __launch_bounds__(256) void update_pos_kernel(int n, int eps_ld, uint
                                                          const float *__restrict__ sigma) {
 #pragma clang fp contract(off)
   const int e = blockIdx.x * 256 + threadIdx.x;
+  const bool live = e < n;
+  // ---- every load that does not need t
   const int t = t_dev[0], step = t_dev[1];
-  if (e < n) {
-    const int ep = eps_ld ? (e / 3) * eps_ld + e % 3 : e;  // eps rows may be padded (the plan's last GEMM output)
-    float v = (x[e] - c_eps[t] * eps[ep]) / sqrt_alpha[t];
-    if (t > 0) {
-      const float z = noise ? noise[(size_t)step * n + e]
-                            : philox_normal(seed_lo, seed_hi, (uint32_t)step, (uint32_t)e + (uint32_t)t_dev[4] * 48u, (uint32_t)t_dev[3]);
-      v = v + sigma[t] * z;
+  const uint32_t nonce = (uint32_t)t_dev[3], eoff = (uint32_t)t_dev[4] * 48u;
+  float xv = 0.f, ev = 0.f;
+  if (live) {
+    xv = x[e];
+    ev = eps[eps_ld ? (e / 3) * eps_ld + e % 3 : e];  // eps rows may be padded (the plan's last GEMM output)
+  }
+  arrived(xv);
+  arrived(ev);
+  t_hold(t, step);
+  __syncthreads();
+  int ticket = 0;
+  if (threadIdx.x == 0) ticket = t_ticket_draw(t_dev);
+  // ---- the coefficients (in flight under the draw)
+  const float ce = c_eps[t], sa = sqrt_alpha[t], sg = sigma[t];
+  float z = 0.f;
+  if (t > 0 && live) {
+    if (noise) {
+      z = noise[(size_t)step * n + e];
+      arrived(z);  // (waited for HERE, so that the path that draws its noise has no wait on loads behind the ticket)
+    } else {
+      z = philox_normal(seed_lo, seed_hi, (uint32_t)step, (uint32_t)e + eoff, nonce);
     }
+  }
+  if (live) {
+    float v = (xv - ce * ev) / sa;
+    if (t > 0) v = v + sg * z;
     x[e] = v;
   }
-  advance_t_last_block(t_dev, t, step);
+  if (threadIdx.x == 0) t_ticket_settle(t_dev, ticket, (int)gridDim.x, t, step);
 }
 
 // denoising_step (pointnet2/diffusion_utils/diffusion.py:58-95) with the key-point channels re-clamped to the
 // condition (:383-385): x0 = rc*x - rm1*eps [clamp]; mean = c1*x0 + c2*x; x = mean + [t>0] std*z
+//
+// A thread is a (point, channel slot): lane l of a wave owns channel blockIdx.y * 64 + l of the wave's EPT consecutive points, so
+// no element pays a division by C and a wave's loads and stores of a point are one contiguous run.  The first
+// UPDATE_STAGED_COPIES SlidePrepCopy descriptors are read ONCE per workgroup, one per lane and together with the other first loads,
+// and cross to the other lanes through LDS behind the barrier the ticket needs anyway (a plan has about six, one of them of kind 0);
+// descriptors beyond those are read from memory per use.
+#ifndef SLIDE_UPDATE_FEAT_EPT
+#define SLIDE_UPDATE_FEAT_EPT 2  // points per wave (profiles/update_kernels.md)
+#endif
+constexpr int UPDATE_STAGED_COPIES = 8;
+
+__device__ __forceinline__ void update_feat_store(void *dst, size_t i, int half_out, float v) {
+  if (half_out) gptr<_Float16>((uint64_t)dst)[i] = (_Float16)v;  // (known GLOBAL: no flat stores through a loaded pointer)
+  else gptr<float>((uint64_t)dst)[i] = v;
+}
+
+template <int EPT>
 __global__ __launch_bounds__(256) void update_feat_kernel(int npts, int C, int kdim, int eps_ld, float clamp, uint32_t seed_lo,
                                                           uint32_t seed_hi, float *__restrict__ x,
                                                           const float *__restrict__ eps, const float *__restrict__ noise,
@@ -350,18 +391,117 @@ __global__ __launch_bounds__(256) void update_feat_kernel(int npts, int C, int k
                                                           const float *__restrict__ kmask, void *__restrict__ feat0, int ldf,
                                                           int half_out, const SlidePrepCopy *__restrict__ copies, int n_copies) {
 #pragma clang fp contract(off)
+  __shared__ u32x4 cps[UPDATE_STAGED_COPIES];
+  const int tid = threadIdx.x, c = blockIdx.y * 64 + (tid & 63);
+  const int p0 = (blockIdx.x * 4 + (tid >> 6)) * EPT;
+  if (!feat0) n_copies = 0;
+  // the integer arguments are fetched in ONE batch ahead of the t_dev read: a wait for a scalar load is a wait for all of them, so
+  // an argument fetched later, where it is first used, would put the t_dev round trip in front of the loads that follow it.
+  // (Not volatile and no memory clobber: either would turn the t_dev read into a vector load.  The pointers stay out: a pointer
+  // that escapes into an asm statement loses its no-alias guarantee, and the coefficient reads would become vector loads.)
+  asm("" : "+s"(npts), "+s"(C), "+s"(kdim), "+s"(eps_ld), "+s"(clamp), "+s"(seed_lo), "+s"(seed_hi), "+s"(ldf), "+s"(half_out),
+      "+s"(n_copies));
+  // ---- every load that does not need t
   const int t = t_dev[0], step = t_dev[1];
   const uint32_t nonce = (uint32_t)t_dev[3];
   // the noise element index is GLOBAL: t_dev[4] = global index of the chain's first sample, so that a shape's noise does not
   // depend on how the run was split into ranks, batches and sub-batch chains
   const uint32_t eoff = (uint32_t)t_dev[4] * (uint32_t)(16 * C);
-  // four elements per thread: a quarter of the blocks queue on the completion counter
+  asm volatile("" ::: "memory");  // (the t_dev read goes out FIRST: no load below may be issued ahead of it)
+  // lane q of the first wave: descriptor q (an absent one re-reads the last).  Nothing else is assigned to my_cp and nothing is
+  // computed from it before the LDS write below: either puts a wait for this load in front of the element loads
+  const bool stager = tid < (n_copies > 0 ? UPDATE_STAGED_COPIES : 0);
+  SlidePrepCopy my_cp;
+  if (stager) my_cp = copies[min(tid, n_copies - 1)];
+  asm volatile("" ::: "memory");
+  float xv[EPT], ev[EPT], cx0[EPT], km[EPT];
 #pragma unroll
-  for (int j = 0; j < 4; ++j)
-    update_feat_element(blockIdx.x * 1024 + j * 256 + threadIdx.x, npts, C, kdim, eps_ld, clamp, seed_lo, seed_hi, x, eps, noise,
-                        t, step, nonce, eoff, complete_x0, kmask, keypoint, rc, rm1, c1, c2, stdv, feat0, ldf, half_out, copies,
-                        n_copies);
-  advance_t_last_block(t_dev, t, step);
+  for (int j = 0; j < EPT; ++j) {
+    const int p = p0 + j, e = p * C + c;
+    xv[j] = ev[j] = cx0[j] = km[j] = 0.f;
+    if (p < npts && c < C) {
+      if (c < kdim) {
+        xv[j] = keypoint[(size_t)p * kdim + c];
+      } else {
+        xv[j] = x[e];
+        if (eps) ev[j] = eps[eps_ld ? (size_t)p * eps_ld + c : (size_t)e];
+        if (complete_x0) {
+          km[j] = kmask[p];
+          cx0[j] = complete_x0[e];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < EPT; ++j) {
+    arrived(xv[j]);
+    arrived(ev[j]);
+    arrived(cx0[j]);
+    arrived(km[j]);
+  }
+  // staged as (dst, ld, n) with n = 0 for an entry that is absent or no feature copy (kind != 0).  The descriptor is opaque up to
+  // here, so that nothing computed from it (and no wait for it) is placed among the loads above
+  if (stager) {
+    asm volatile("" : "+v"(my_cp.dst), "+v"(my_cp.ld), "+v"(my_cp.kind), "+v"(my_cp.n)::"memory");
+    cps[tid] = u32x4{(uint32_t)(uint64_t)my_cp.dst, (uint32_t)((uint64_t)my_cp.dst >> 32), (uint32_t)my_cp.ld,
+                     tid < n_copies && my_cp.kind == 0 ? (uint32_t)max(my_cp.n, 0) : 0u};
+  } else if (tid < UPDATE_STAGED_COPIES) {
+    cps[tid] = u32x4{0u, 0u, 0u, 0u};
+  }
+  t_hold(t, step);
+  __syncthreads();  // (every wave of the workgroup holds t and step; cps is staged)
+  int ticket = 0;
+  if (tid == 0) ticket = t_ticket_draw(t_dev);
+  u32x4 cp[UPDATE_STAGED_COPIES];
+#pragma unroll
+  for (int q = 0; q < UPDATE_STAGED_COPIES; ++q) cp[q] = cps[q];
+  // ---- the coefficients (in flight under the draw)
+  const float k_rc = rc[t], k_rm1 = rm1[t], k_c1 = c1[t], k_c2 = c2[t], k_std = stdv[t];
+  float z[EPT];
+#pragma unroll
+  for (int j = 0; j < EPT; ++j) {
+    const int p = p0 + j, e = p * C + c;
+    z[j] = 0.f;
+    if (t > 0 && p < npts && c >= kdim && c < C) {
+      if (noise) {
+        z[j] = noise[(size_t)step * npts * C + e];
+        arrived(z[j]);  // (waited for HERE, so that the path that draws its noise has no wait on loads behind the ticket)
+      } else {
+        z[j] = philox_normal(seed_lo, seed_hi, (uint32_t)step, (uint32_t)e + eoff, nonce);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < EPT; ++j) {
+    const int p = p0 + j, e = p * C + c;
+    if (p >= npts || c >= C) continue;
+    if (c < kdim) {
+      x[e] = xv[j];
+      continue;
+    }
+    float x0 = k_rc * xv[j] - k_rm1 * ev[j];
+    if (clamp > 0.f) x0 = fminf(fmaxf(x0, -clamp), clamp);
+    if (complete_x0)  // local re-sampling (diffusion.py:76-79): pred_xstart*mask + complete_x0*(1-mask), mask per point
+      x0 = x0 * km[j] + cx0[j] * (1.f - km[j]);
+    float v = k_c1 * x0 + k_c2 * xv[j];
+    if (t > 0) v = v + k_std * z[j];
+    x[e] = v;
+    // fixed key points (kdim == 3): the feature column of the per-point table and of the concatenation buffers that the NEXT
+    // step's point preparation would derive from this element (update_feat_element)
+    if (feat0) {
+      const int cf = c - kdim;
+      update_feat_store(feat0, (size_t)p * ldf + cf, half_out, v);
+#pragma unroll
+      for (int q = 0; q < UPDATE_STAGED_COPIES; ++q)
+        if (cf < (int)cp[q][3])
+          update_feat_store((void *)((uint64_t)cp[q][1] << 32 | cp[q][0]), (size_t)p * (int)cp[q][2] + cf, half_out, v);
+      for (int q = UPDATE_STAGED_COPIES; q < n_copies; ++q) {
+        const SlidePrepCopy cp = copies[q];
+        if (cp.kind == 0 && cf < cp.n) update_feat_store(cp.dst, (size_t)p * cp.ld + cf, half_out, v);
+      }
+    }
+  }
+  if (tid == 0) t_ticket_settle(t_dev, ticket, (int)(gridDim.x * gridDim.y), t, step);
 }
 
 // ------------------------------------------------------------------------------------------------ output head + DDPM update
@@ -629,7 +769,8 @@ int run_op(const SlideOp &o, hipStream_t s) {
                          (int *)o.p[3], (const float *)o.p[4], (const float *)o.p[5], (const float *)o.p[6]);
       break;
     case SLIDE_OP_UPDATE_FEAT:
-      hipLaunchKernelGGL(update_feat_kernel, dim3((o.i[0] * o.i[1] + 1023) / 1024), dim3(256), 0, s, o.i[0], o.i[1],
+      hipLaunchKernelGGL(update_feat_kernel<SLIDE_UPDATE_FEAT_EPT>,
+                         dim3((o.i[0] + 4 * SLIDE_UPDATE_FEAT_EPT - 1) / (4 * SLIDE_UPDATE_FEAT_EPT), (o.i[1] + 63) / 64), dim3(256), 0, s, o.i[0], o.i[1],
                          o.i[2], o.i[5], o.f[0], (uint32_t)o.i[3], (uint32_t)o.i[4], (float *)o.p[0], (const float *)o.p[1],
                          (const float *)o.p[2], (int *)o.p[3], (const float *)o.p[4], (const float *)o.p[5],
                          (const float *)o.p[6], (const float *)o.p[7], (const float *)o.p[8], (const float *)o.p[9],
