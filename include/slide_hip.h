@@ -19,7 +19,7 @@
  *
  * Part 4 is the Chamfer / F1 metric (the reference's pointnet2/metrics_point_cloud/chamfer_and_f1.py, forward only).
  *
- * Part 5 is DPSR, oriented points to the Poisson indicator grid (the reference's pointnet2/dpsr_utils/dpsr.py, forward only).
+ * Part 5 is DPSR, oriented points to the Poisson indicator grid (the reference's pointnet2/dpsr_utils/dpsr.py), forward and backward.
  *
  * Part 3 is the fused latent-DDPM denoiser engine (the reference runs these as ~80 torch module
  * launches per step: pointnet2/models/pointnet2_with_pcld_condition.py:286-489).
@@ -180,6 +180,36 @@ SLIDE_API int slide_dpsr_finish(int b, int n, int r, const float *fv, int shift,
 SLIDE_API int slide_dpsr_grid(int b, int n, int r, const float *pts, const float *normals, const float *g, int shift, int scale,
                               long long *ws_grid, float *ws_spec, float *ws_phis, float *ws_fv, float *ws_coef, float *phi, int *flag,
                               slide_stream_t stream);
+
+/* The backward of slide_dpsr_grid (csrc/dpsr_bwd.hip, where the mathematics is written out): gout = dL/dphi (b,r,r,r) -> dv, dn
+ * (b,n,3), the gradients of pts and normals.  phi (b,r,r,r) is the forward's output and coef (b,2) what it left in ws_coef.  No
+ * atomics but the integer ones of slide_point_rasterize: every result is bit-reproducible and does not depend on b or on a
+ * sample's position.
+ *
+ * Per-sample sums in double, fixed order: sums (b,2) = (sum gout, sum gout * phi) over a sample's r^3 cells.  ws_part (b, nbps, 2)
+ * double with nbps = ceil(r^3 / 4096).  Two launches.  2 <= r <= 1024. */
+SLIDE_API int slide_dpsr_bwd_sums(int b, int r, const float *gout, const float *phi, double *ws_part, double *sums,
+                                  slide_stream_t stream);
+/* The adjoint of slide_dpsr_finish and of the shift, elementwise: gout, phi, sums, coef and, with shift, w (b,r,r,r) int64 =
+ * slide_point_rasterize(pts, 1.0) -> dpre (b,r,r,r) f32, the gradient of the grid before shift and scale.  Without shift and scale
+ * it copies gout; phi, sums, coef may then be NULL, and w whenever shift is 0. */
+SLIDE_API int slide_dpsr_bwd_dpre(int b, int n, int r, const float *gout, const float *phi, const double *sums, const float *coef,
+                                  const long long *w, int shift, int scale, float *dpre, slide_stream_t stream);
+/* The adjoint of slide_dpsr_spectral: spec (b,r,r,h) complex = slide_fft3_r2c(dpre), g (r,r,h) -> out (b,3,r,r,h) complex,
+ * +i omega_d g spec / (-|omega|^2 + 1e-6), bin (0,0,0) = 0; slide_fft3_c2r of it is the gradient of the rasterized normals. */
+SLIDE_API int slide_dpsr_spectral_adj(int b, int r, const float *spec, const float *g, float *out, slide_stream_t stream);
+/* One thread per point: dras (b,3,r,r,r) f32 and, with shift, phi, sums and coef -> dv, dn (b,n,3); either may be NULL (0 without a
+ * launch when both are).  flag as in slide_grid_interp; a point left out gets zeros. */
+SLIDE_API int slide_dpsr_bwd_points(int b, int n, int r, const float *pts, const float *normals, const float *dras, const float *phi,
+                                    const double *sums, const float *coef, int shift, int scale, float *dv, float *dn, int *flag,
+                                    slide_stream_t stream);
+/* All of it for b samples.  Workspaces of the caller: ws_w (b,r,r,r) int64 and ws_ones (b,n) f32 (both filled here; NULL allowed
+ * without shift), ws_dpre (b,r,r,r) f32, ws_spec (b,r,r,h) complex, ws_spec3 (b,3,r,r,h) complex, ws_dras (b,3,r,r,r) f32, ws_part
+ * and ws_sums as above (NULL allowed without shift and scale, like coef).  r in {16, 32, 64, 128, 256}, n >= 1. */
+SLIDE_API int slide_dpsr_grid_bwd(int b, int n, int r, const float *pts, const float *normals, const float *g, const float *phi,
+                                  const float *coef, const float *gout, int shift, int scale, long long *ws_w, float *ws_ones,
+                                  float *ws_dpre, float *ws_spec, float *ws_spec3, float *ws_dras, double *ws_part, double *ws_sums,
+                                  float *dv, float *dn, int *flag, slide_stream_t stream);
 
 /* ------------------------------------------------------------------ Part 3: denoiser engine */
 /* see slide_engine.h */

@@ -561,35 +561,153 @@ def dpsr_chunk(r, n, chunk=None):
     return max(1, _DPSR_WORKSPACE_BYTES // per)
 
 
-def dpsr_grid(pts, normals, G, shift=True, scale=True, chunk=None):
-    """DPSR.forward on the composed entry point (slide_dpsr_grid): pts / normals (B,n,3) f32, G the filter of r*r*(r/2+1) floats of
-    shape (r,r,r/2+1,...) -> phi (B,r,r,r) f32.  Samples run `chunk` at a time (default: dpsr_chunk); a sample's grid does not depend
-    on the chunk or the batch.  One host read of a flag word at the end: ValueError for a point the kernels rejected."""
-    pts, normals = _pts_vals(pts, normals, "dpsr_grid")
+def _dpsr_args(pts, normals, G, what):
+    pts, normals = _pts_vals(pts, normals, what)
     if normals.size(2) != 3 or pts.size(1) < 1:
-        raise ValueError("dpsr_grid: normals (B,n,3) with n >= 1 expected, got %s" % (tuple(normals.shape),))
+        raise ValueError("%s: normals (B,n,3) with n >= 1 expected, got %s" % (what, tuple(normals.shape)))
     G = _chk_f32_cuda(G, "G")
     r = G.size(0)
     _chk_fft_size(r)
+    if G.numel() != r * r * (r // 2 + 1):
+        raise ValueError("%s: G must hold r*r*(r/2+1) values" % what)
+    return pts, normals, G, r
+
+
+def dpsr_grid(pts, normals, G, shift=True, scale=True, chunk=None, return_coef=False):
+    """DPSR.forward on the composed entry point (slide_dpsr_grid): pts / normals (B,n,3) f32, G the filter of r*r*(r/2+1) floats of
+    shape (r,r,r/2+1,...) -> phi (B,r,r,r) f32.  Samples run `chunk` at a time (default: dpsr_chunk); a sample's grid does not depend
+    on the chunk or the batch.  One host read of a flag word at the end: ValueError for a point the kernels rejected.
+    return_coef: -> (phi, coef (B,2) f32), coef = (offset, |phi[0,0,0] - offset|) per sample as slide_dpsr_finish computes them
+    (zeros without shift and scale) -- what dpsr_grid_backward needs; the launches and phi's bits are the same."""
+    pts, normals, G, r = _dpsr_args(pts, normals, G, "dpsr_grid")
     h = r // 2 + 1
-    if G.numel() != r * r * h:
-        raise ValueError("dpsr_grid: G must hold r*r*(r/2+1) values")
     B, n = pts.size(0), pts.size(1)
     dev = pts.device
     phi = torch.empty((B, r, r, r), device=dev, dtype=torch.float32)
+    coef = torch.zeros((B, 2), device=dev, dtype=torch.float32) if return_coef else None
     if B == 0:
-        return phi
+        return (phi, coef) if return_coef else phi
     cb = min(dpsr_chunk(r, n, chunk), B)
     ws_grid = torch.empty((cb, 3, r, r, r), device=dev, dtype=torch.int64)
     ws_spec = torch.empty((cb, 3, r, r, h, 2), device=dev, dtype=torch.float32)
     ws_phis = torch.empty((cb, r, r, h, 2), device=dev, dtype=torch.float32)
     ws_fv = torch.empty((cb, n), device=dev, dtype=torch.float32)
-    ws_coef = torch.empty((cb, 2), device=dev, dtype=torch.float32)
+    ws_coef = None if return_coef else torch.empty((cb, 2), device=dev, dtype=torch.float32)
     flag = torch.zeros(1, device=dev, dtype=torch.int32)
     for s in range(0, B, cb):
         e = min(s + cb, B)
         check(lib().slide_dpsr_grid(e - s, n, r, ptr(pts[s:e]), ptr(normals[s:e]), ptr(G), int(shift), int(scale), ptr(ws_grid),
-                                    ptr(ws_spec), ptr(ws_phis), ptr(ws_fv), ptr(ws_coef), ptr(phi[s:e]), ptr(flag), stream_of()),
+                                    ptr(ws_spec), ptr(ws_phis), ptr(ws_fv), ptr(coef[s:e] if return_coef else ws_coef), ptr(phi[s:e]),
+                                    ptr(flag), stream_of()),
               "dpsr_grid")
     _raise_dpsr_flag(flag, "dpsr_grid")
-    return phi
+    return (phi, coef) if return_coef else phi
+
+
+def dpsr_bwd_sum_blocks(r):
+    """workgroups per sample of the first stage of slide_dpsr_bwd_sums"""
+    return (r ** 3 + 4095) // 4096
+
+
+def dpsr_bwd_sums(g, phi):
+    """per-sample (sum g, sum g * phi) in double, fixed order (slide_dpsr_bwd_sums): g, phi (B,r,r,r) f32 -> (B,2) f64"""
+    g = _chk_f32_cuda(g, "g", 4)
+    phi = _chk_f32_cuda(phi, "phi", 4)
+    if g.shape != phi.shape:
+        raise ValueError("dpsr_bwd_sums: g and phi must have the same shape")
+    B, r = g.size(0), g.size(1)
+    part = torch.empty((B, dpsr_bwd_sum_blocks(r), 2), device=g.device, dtype=torch.float64)
+    sums = torch.empty((B, 2), device=g.device, dtype=torch.float64)
+    check(lib().slide_dpsr_bwd_sums(B, r, ptr(g), ptr(phi), ptr(part), ptr(sums), stream_of()), "dpsr_bwd_sums")
+    return sums
+
+
+def dpsr_bwd_dpre(g, phi, sums, coef, w, n, shift=True, scale=True):
+    """the adjoint of the finish and the shift (slide_dpsr_bwd_dpre): g, phi (B,r,r,r) f32, sums (B,2) f64, coef (B,2) f32, w
+    (B,r,r,r) int64 = point_rasterize_fixed(pts, ones) or None without shift -> dpre (B,r,r,r) f32"""
+    g = _chk_f32_cuda(g, "g", 4)
+    phi = _chk_f32_cuda(phi, "phi", 4)
+    B, r = g.size(0), g.size(1)
+    if shift and (w is None or w.dtype != torch.int64 or w.numel() != g.numel()):
+        raise ValueError("dpsr_bwd_dpre: with shift, w must be the int64 density grid of g's size")
+    out = torch.empty_like(g)
+    check(lib().slide_dpsr_bwd_dpre(B, n, r, ptr(g), ptr(phi), ptr(sums), ptr(coef), ptr(w.contiguous()) if shift else None, int(shift),
+                                    int(scale), ptr(out), stream_of()), "dpsr_bwd_dpre")
+    return out
+
+
+def dpsr_spectral_adj(spec, G):
+    """the adjoint of dpsr_spectral (slide_dpsr_spectral_adj): spec (B,r,r,h) complex64, G r*r*h f32 -> (B,3,r,r,h) complex64"""
+    if not spec.is_cuda or spec.dtype != torch.complex64 or spec.dim() != 4:
+        raise RuntimeError("dpsr_spectral_adj: a CUDA complex64 tensor (B,r,r,h) is expected")
+    B, r = spec.size(0), spec.size(1)
+    _chk_fft_size(r)
+    G = _chk_f32_cuda(G, "G")
+    if G.numel() != r * r * (r // 2 + 1) or tuple(spec.shape[1:]) != (r, r, r // 2 + 1):
+        raise ValueError("dpsr_spectral_adj: spec (B,r,r,r/2+1) and G of r*r*(r/2+1) values expected")
+    s = torch.view_as_real(spec.contiguous())
+    out = torch.empty((B, 3, r, r, r // 2 + 1, 2), device=spec.device, dtype=torch.float32)
+    check(lib().slide_dpsr_spectral_adj(B, r, ptr(s), ptr(G), ptr(out), stream_of()), "dpsr_spectral_adj")
+    return torch.view_as_complex(out)
+
+
+def dpsr_bwd_points(pts, normals, dras, phi=None, sums=None, coef=None, shift=False, scale=False, need_v=True, need_n=True):
+    """the per-point gather of the backward (slide_dpsr_bwd_points): pts / normals (B,n,3), dras (B,3,r,r,r) f32 and, with shift,
+    phi (B,r,r,r), sums (B,2) f64, coef (B,2) -> (dV, dN), each (B,n,3) or None when not needed"""
+    pts, normals = _pts_vals(pts, normals, "dpsr_bwd_points")
+    dras = _chk_f32_cuda(dras, "dras", 5)
+    B, n, r = pts.size(0), pts.size(1), dras.size(2)
+    if normals.size(2) != 3 or tuple(dras.shape) != (B, 3, r, r, r):
+        raise ValueError("dpsr_bwd_points: normals (B,n,3) and dras (B,3,r,r,r) expected")
+    if shift:
+        phi = _chk_f32_cuda(phi, "phi", 4)
+        if tuple(phi.shape) != (B, r, r, r):
+            raise ValueError("dpsr_bwd_points: phi (B,r,r,r) expected")
+    dv = torch.empty_like(pts) if need_v else None
+    dn = torch.empty_like(pts) if need_n else None
+    flag = torch.zeros(1, device=pts.device, dtype=torch.int32)
+    check(lib().slide_dpsr_bwd_points(B, n, r, ptr(pts), ptr(normals), ptr(dras), ptr(phi) if shift else None,
+                                      ptr(sums) if shift else None, ptr(coef) if shift else None, int(shift), int(scale),
+                                      ptr(dv) if need_v else None, ptr(dn) if need_n else None, ptr(flag), stream_of()), "dpsr_bwd_points")
+    if B and n and (need_v or need_n):
+        _raise_dpsr_flag(flag, "dpsr_bwd_points")
+    return dv, dn
+
+
+def dpsr_grid_backward(pts, normals, G, phi, coef, g, shift=True, scale=True, need_v=True, need_n=True, chunk=None):
+    """the backward of dpsr_grid on the composed entry point (slide_dpsr_grid_bwd): phi, coef = dpsr_grid(..., return_coef=True),
+    g = dL/dphi (B,r,r,r) f32 -> (dV, dN), each (B,n,3) f32 or None when not needed.  Samples run `chunk` at a time exactly as in
+    dpsr_grid (the workspace per sample is the forward's); a sample's gradients do not depend on the chunk or the batch."""
+    pts, normals, G, r = _dpsr_args(pts, normals, G, "dpsr_grid_backward")
+    phi = _chk_f32_cuda(phi, "phi", 4)
+    g = _chk_f32_cuda(g, "g", 4)
+    coef = _chk_f32_cuda(coef, "coef", 2)
+    B, n = pts.size(0), pts.size(1)
+    if tuple(phi.shape) != (B, r, r, r) or g.shape != phi.shape or tuple(coef.shape) != (B, 2):
+        raise ValueError("dpsr_grid_backward: phi and g (B,r,r,r) and coef (B,2) expected, got %s, %s and %s" % (
+            tuple(phi.shape), tuple(g.shape), tuple(coef.shape)))
+    dev = pts.device
+    dv = torch.empty_like(pts) if need_v else None
+    dn = torch.empty_like(pts) if need_n else None
+    if B == 0 or not (need_v or need_n):
+        return dv, dn
+    h = r // 2 + 1
+    cb = min(dpsr_chunk(r, n, chunk), B)
+    ws_w = torch.empty((cb, r, r, r), device=dev, dtype=torch.int64) if shift else None
+    ws_ones = torch.empty((cb, n), device=dev, dtype=torch.float32) if shift else None
+    ws_dpre = torch.empty((cb, r, r, r), device=dev, dtype=torch.float32)
+    ws_spec = torch.empty((cb, r, r, h, 2), device=dev, dtype=torch.float32)
+    ws_spec3 = torch.empty((cb, 3, r, r, h, 2), device=dev, dtype=torch.float32)
+    ws_dras = torch.empty((cb, 3, r, r, r), device=dev, dtype=torch.float32)
+    ws_part = torch.empty((cb, dpsr_bwd_sum_blocks(r), 2), device=dev, dtype=torch.float64)
+    ws_sums = torch.empty((cb, 2), device=dev, dtype=torch.float64)
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    for s in range(0, B, cb):
+        e = min(s + cb, B)
+        check(lib().slide_dpsr_grid_bwd(e - s, n, r, ptr(pts[s:e]), ptr(normals[s:e]), ptr(G), ptr(phi[s:e]), ptr(coef[s:e]), ptr(g[s:e]),
+                                        int(shift), int(scale), ptr(ws_w) if shift else None, ptr(ws_ones) if shift else None,
+                                        ptr(ws_dpre), ptr(ws_spec), ptr(ws_spec3), ptr(ws_dras), ptr(ws_part), ptr(ws_sums),
+                                        ptr(dv[s:e]) if need_v else None, ptr(dn[s:e]) if need_n else None, ptr(flag), stream_of()),
+              "dpsr_grid_backward")
+    _raise_dpsr_flag(flag, "dpsr_grid_backward")
+    return dv, dn

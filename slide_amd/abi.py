@@ -179,6 +179,11 @@ PROTOTYPES = {name: _proto(args) for name, args in {
     "slide_dpsr_spectral": "iipppp",
     "slide_dpsr_finish": "iiipiippp",
     "slide_dpsr_grid": "iiipppiipppppppp",
+    "slide_dpsr_bwd_sums": "iippppp",
+    "slide_dpsr_bwd_dpre": "iiipppppiipp",
+    "slide_dpsr_spectral_adj": "iipppp",
+    "slide_dpsr_bwd_points": "iiippppppiipppp",
+    "slide_dpsr_grid_bwd": "iiippppppii" + "p" * 12,
     "slide_hip_device_ok": "",
     "slide_lane_reduce_selftest": "pppip",
     "slide_philox_normal_selftest": "iiiiiipp",

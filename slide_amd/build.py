@@ -29,7 +29,8 @@ NO_ATOMIC_OPT = ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]
 SOURCES = [("point_ops.hip", ["-ffp-contract=off"]), ("chamfer.hip", ["-ffp-contract=off"]),
            ("chamfer_pairwise.hip", ["-ffp-contract=off"]), ("chamfer_bwd.hip", ["-ffp-contract=off"]),
            ("occupancy_grid.hip", ["-ffp-contract=off"]), ("emd_pairwise.hip", ["-ffp-contract=off"]),
-           ("dpsr.hip", ["-ffp-contract=off"]), ("engine.hip", UNROLL + NO_ATOMIC_OPT), ("gemm_ring.hip", UNROLL), ("attn_tail.hip", UNROLL),
+           ("dpsr.hip", ["-ffp-contract=off"]), ("dpsr_bwd.hip", ["-ffp-contract=off"]),
+           ("engine.hip", UNROLL + NO_ATOMIC_OPT), ("gemm_ring.hip", UNROLL), ("attn_tail.hip", UNROLL),
            ("gemm_gx.hip", UNROLL), ("gemm_gxs.hip", UNROLL),
            ("point_chain.hip", UNROLL), ("rows_ops.hip", []), ("train_ops.hip", []), ("encoder_ops.hip", []),
            ("group_coord_bwd.hip", ["-ffp-contract=off"]), ("lane_reduce_selftest.hip", []), ("philox_selftest.hip", [])]

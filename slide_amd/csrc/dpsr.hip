@@ -1,4 +1,5 @@
-// dpsr.hip -- differentiable Poisson surface reconstruction, forward only: oriented points -> the Poisson indicator grid
+// dpsr.hip -- differentiable Poisson surface reconstruction, the forward: oriented points -> the Poisson indicator grid (the
+// backward is dpsr_bwd.hip)
 // (pointnet2/dpsr_utils/dpsr.py: DPSR.forward; the reference's pointnet2/dpsr_utils/dpsr.py + utils.py, where torch index
 // arithmetic, scatter_add_, torch.fft.rfftn / irfftn and fancy-index gathers do this work).
 //
@@ -31,47 +32,12 @@
 #include <stdint.h>
 
 #include "../../include/slide_hip.h"
-
-#define LAUNCH_STATUS() ((int)hipGetLastError())
+#include "dpsr_cell.h"  // NT, the fixed-point scale, cell_of, log2_fft, blocks_ok / blocks_of
 
 namespace {
 
-constexpr int NT = 256;
 constexpr int FFT_TILE = 2048;                       // complex elements of one LDS buffer
 constexpr int FFT_RMAX = 256;
-constexpr double FIX_ONE = 4294967296.0;             // 2^32
-constexpr float FIX_INV = 2.3283064365386963e-10f;   // 2^-32
-constexpr float VAL_MAX = 1048576.0f;                // 2^20
-constexpr int GRID_RMAX = 1024;                      // r^3 stays within 2^30
-
-// the cell of a point: flat indices and weights of its 8 corners; false when a coordinate is not in [0, 1)
-__device__ __forceinline__ bool cell_of(float px, float py, float pz, int r, int (&idx)[8], float (&w)[8]) {
-  const float p[3] = {px, py, pz};
-  const float fr = (float)r;
-  const float cs = 1.0f / fr;
-  int i0[3], i1[3];
-  float wa[3], wb[3];
-  bool ok = true;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    ok = ok && (p[d] >= 0.0f) && (p[d] < 1.0f);  // (a NaN fails both)
-    const float q = p[d] / cs;
-    const float f0 = floorf(q);
-    i0[d] = (int)f0;
-    i1[d] = (int)fmodf(ceilf(q), fr);
-    ok = ok && (i0[d] < r);  // (p / cs can round up to r when r is no power of two)
-    wa[d] = fabsf(p[d] - (f0 + 1.0f) * cs) / cs;  // corner bit 0: the opposite corner is (ind0 + 1) * cs
-    wb[d] = fabsf(p[d] - f0 * cs) / cs;           // corner bit 1: the opposite corner is ind0 * cs
-  }
-  if (!ok) return false;
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const int b0 = c >> 2, b1 = (c >> 1) & 1, b2 = c & 1;
-    idx[c] = ((b0 ? i1[0] : i0[0]) * r + (b1 ? i1[1] : i0[1])) * r + (b2 ? i1[2] : i0[2]);
-    w[c] = ((b0 ? wb[0] : wa[0]) * (b1 ? wb[1] : wa[1])) * (b2 ? wb[2] : wa[2]);
-  }
-  return true;
-}
 
 // ------------------------------------------------------------------------------------------------------------ rasterize
 template <int NF>
@@ -302,20 +268,10 @@ __global__ __launch_bounds__(NT) void dpsr_finish_kernel(long long total, long l
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side
-inline int log2_fft(int r) {
-  for (int lg = 4; lg <= 8; ++lg)
-    if (r == (1 << lg)) return lg;
-  return -1;
-}
-
 inline int tile_log2(int lg) {  // T = min(FFT_TILE / r, 32) lines
   const int lgT = 11 - lg;
   return lgT > 5 ? 5 : lgT;
 }
-
-inline bool blocks_ok(long long nblk) { return nblk > 0 && nblk <= 0x7fffffffLL; }
-
-inline unsigned blocks_of(long long total) { return (unsigned)((total + NT - 1) / NT); }
 
 int strided_pass(float2 *x, long long outer, long long inner, int lg, int inverse, hipStream_t st) {
   const int lgT = tile_log2(lg);

@@ -394,6 +394,44 @@ def chamfer_cd(output, gt, f1_threshold=1e-4):
     return ChamferCD.apply(output, gt, float(f1_threshold))
 
 
+class DpsrGrid(torch.autograd.Function):
+    """DPSR.forward (pointnet2/dpsr_utils/dpsr.py): V, N (B, n, 3) and the filter G -> phi (B, r, r, r), bit-equal to _ext.dpsr_grid.
+    Saves V, N, phi and the per-sample (offset, |fv0|) only (G is the module's buffer, held by reference); backward: csrc/dpsr_bwd.hip (include/slide_hip.h slide_dpsr_grid_bwd) on the
+    same chunks.  G gets no gradient; no double backward."""
+
+    @staticmethod
+    def forward(ctx, V, N, G, shift, scale, chunk):
+        V, N, G = V.detach().contiguous(), N.detach().contiguous(), G.detach()
+        phi, coef = _ext.dpsr_grid(V, N, G, shift=shift, scale=scale, chunk=chunk, return_coef=True)
+        ctx.save_for_backward(V, N, G, phi, coef)
+        ctx.flags = (bool(shift), bool(scale), chunk)
+        return phi
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():  # (create_graph=True: the engine runs backward functions with grad mode on)
+            raise RuntimeError("DpsrGrid: double backward is not supported (the backward kernels are not differentiable)")
+        V, N, G, phi, coef = ctx.saved_tensors
+        shift, scale, chunk = ctx.flags
+        # (contiguous(): the gradient of a sum or a mean arrives as an expanded scalar)
+        dV, dN = _ext.dpsr_grid_backward(V, N, G, phi, coef, g.contiguous(), shift=shift, scale=scale, need_v=ctx.needs_input_grad[0],
+                                         need_n=ctx.needs_input_grad[1], chunk=chunk)
+        return dV, dN, None, None, None, None
+
+
+def dpsr_grid(V, N, G, shift=True, scale=True, chunk=None):
+    """differentiable DPSR: V (B, n, 3) coordinates in [0, 1), N (B, n, 3) normals, fp32 CUDA tensors, G the module's Gaussian filter
+    (r, r, r/2 + 1, ...) -> phi (B, r, r, r); differentiable in V and N, once."""
+    for t in (V, N):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise RuntimeError("CPU not supported: DPSR launches HIP kernels")
+        if t.dtype != torch.float32:
+            raise RuntimeError("DPSR takes float32 tensors")
+    if V.shape != N.shape:
+        raise ValueError("V and N must have the same shape, got %s and %s" % (tuple(V.shape), tuple(N.shape)))
+    return DpsrGrid.apply(V, N, G, bool(shift), bool(scale), chunk)
+
+
 class ColMaxSeg(torch.autograd.Function):
     """max over the S rows of each sample of x [B * S, ld] -> [B, ld] (columns >= C zero): the point-wise maxima of Pnet2Stage
     (pointnet2/models/pnet.py:32-40).  One launch forward (slide_col_max_seg: the value and the first row that attains it), one

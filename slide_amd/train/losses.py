@@ -2,7 +2,7 @@
 callable net(x_t, ts, label) -> eps prediction).  Random timesteps and noise are drawn here unless they are passed in (the parity
 tests inject the reference's); and the autoencoder's Chamfer losses (calc_cd_loss, autoencoder_losses) on the differentiable
 Chamfer sums of functions.ChamferCD, with the decode side's training loss (decoder_training_loss) and the whole autoencoder's
-(autoencoder_training_loss) on top."""
+(autoencoder_training_loss) on top; and the refinement network's grid loss through DPSR (psr_grid_loss)."""
 import numpy as np
 import torch
 
@@ -158,3 +158,22 @@ def decoder_training_loss(decoder, keypoint, feature_at_keypoint, label, pointcl
     l_xyz_decoder = decoder.decode(keypoint, feature_at_keypoint, label, fps_start_idx=fps_start_idx)
     loss_list = autoencoder_losses(l_xyz_decoder, pointcloud, feature_weight, loss_type=loss_type, fps_start_idx=fps_start_idx)
     return _sum_of_level_means(loss_list), loss_list
+
+
+def psr_grid_loss(points, normals, psr_gt, dpsr, scale=1, explicit_normalize=False, psr_tanh=False):
+    """the refinement network's training loss on given refined points: the tail of network_output_to_dpsr_grid
+    (pointnet2/dpsr_evaluation.py:77-84: shapenet_psr_normalize or the division by the dataset scale, clamp(x / 1.2 + 0.5, 0, 0.99),
+    DPSR) and the loss of pointnet2/train_upsampler.py (tanh on both grids with psr_tanh, then nn.MSELoss).  points / normals
+    (B, N, 3) fp32 CUDA, psr_gt (B, r, r, r), dpsr a pointnet2 dpsr_utils.dpsr.DPSR -> scalar; differentiable in points and normals
+    (the clamp and the tanh are torch ops, DPSR is functions.DpsrGrid)."""
+    if explicit_normalize:
+        minn = points.min(dim=1, keepdim=True)[0]
+        maxx = points.max(dim=1, keepdim=True)[0]
+        points = (points - (maxx + minn) / 2) / (maxx - minn).max(dim=2, keepdim=True)[0] * 0.99  # shapenet_psr_normalize
+    else:
+        points = points / scale / 2
+    points = torch.clamp(points / 1.2 + 0.5, min=0, max=0.99)
+    psr_grid = dpsr(points.contiguous(), normals.contiguous())
+    if psr_tanh:
+        psr_grid, psr_gt = torch.tanh(psr_grid), torch.tanh(psr_gt)
+    return torch.nn.functional.mse_loss(psr_grid, psr_gt)
