@@ -163,11 +163,11 @@ enum {
   SLIDE_OP_SA_CHAIN_P = 35, /* an SA block's fused Mlp chain (SLIDE_OP_SA_CHAIN) and the per-point query GEMM of its attention (SLIDE_OP_GEMM, 16 rows per
                              * sample, input affine + statistics finalisation) in ONE launch -- both depend on the block's pair tables only:
                              * p[0] = HOST pointer to the two SlideOp (chain first), kept alive by the plan */
-  SLIDE_OP_PP_STAGE = 36,   /* split plans (round 5, csrc/gemm_gxs.hip): a run of consecutive per-point launches of one block -- 16-rows-per-sample
+  SLIDE_OP_PP_STAGE = 36,   /* split plans (round 5, csrc/experiments/pp_stage.hip): a run of consecutive per-point launches of one block -- 16-rows-per-sample
                              * SLIDE_OP_GEMM in the split arithmetic (no gather / statistics finalisation / per-point pre_add) and SLIDE_OP_PAIR_NORM
                              * version 2 on float tables -- as ONE launch, one workgroup per sample walking the steps; the dense layers are exact
                              * fp32 FMA chains on the vector ALUs.  p[0] = HOST pointer to {int64 n, B; n records of 16 int64 slots} (device
-                             * pointers inside; layout in csrc/gemm_gxs.hip slide_launch_pp_stage), kept alive by the plan.  i: B, n */
+                             * pointers inside; layout in csrc/experiments/pp_stage.hip slide_launch_pp_stage), kept alive by the plan.  i: B, n */
   SLIDE_OP_POINT_CHAIN = 37,/* round 5 (csrc/point_chain.hip): the per-point END of a denoiser step as one launch -- the last FP block's second
                              * Mlp (first_mlp + res_connect, second_mlp + fc_condition + residual: pointnet2_modules.py:119-176, :842-855) and the
                              * output head fc_lyaer (pointnet2_with_pcld_condition.py:480-483), four dependent 16-rows-per-sample GEMMs; writes

@@ -14,7 +14,7 @@ LIB = os.path.join(HERE, "libslide_hip.so")
 # EXPERIMENTS build (-DSLIDE_EXPERIMENTS): the product sources + every opt-in variant that lost its A/B (X-stationary GEMM,
 # per-point layer chains, LDS-resident position denoiser, head + update launch, wide / eight-wave attention tails, 128- / 32-
 # channel and 64-deep ring tiles, the round-2 plan's kernels, the register-staged fp16 GEMM, the SA0 block body, the two-launch
-# pair-table pass).  Loaded instead of the product library with SLIDE_EXPERIMENTS=1 or `slide_amd._lib.experiments()`;
+# pair-table pass, the per-point stage).  Loaded instead of the product library with SLIDE_EXPERIMENTS=1 or `slide_amd._lib.experiments()`;
 # the plan-variant tests use it.  Its kernels may spill; the PRODUCT library may not.
 LIB_EXP = os.path.join(HERE, "libslide_hip_exp.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -31,11 +31,12 @@ SOURCES = [("point_ops.hip", ["-ffp-contract=off"]), ("chamfer.hip", ["-ffp-cont
            ("occupancy_grid.hip", ["-ffp-contract=off"]), ("emd_pairwise.hip", ["-ffp-contract=off"]),
            ("dpsr.hip", ["-ffp-contract=off"]), ("dpsr_bwd.hip", ["-ffp-contract=off"]),
            ("engine.hip", UNROLL + NO_ATOMIC_OPT), ("gemm_ring.hip", UNROLL), ("attn_tail.hip", UNROLL),
-           ("gemm_gx.hip", UNROLL), ("gemm_gxs.hip", UNROLL),
-           ("point_chain.hip", UNROLL), ("rows_ops.hip", []), ("train_ops.hip", []), ("encoder_ops.hip", []),
+           ("attn_tail_split.hip", UNROLL), ("gemm_gx.hip", UNROLL), ("pair_norm.hip", UNROLL), ("sa_chain.hip", UNROLL),
+           ("gemm_gxs.hip", UNROLL), ("point_chain.hip", UNROLL), ("rows_ops.hip", []), ("train_ops.hip", []), ("encoder_ops.hip", []),
            ("group_coord_bwd.hip", ["-ffp-contract=off"]), ("lane_reduce_selftest.hip", []), ("philox_selftest.hip", [])]
 SOURCES_EXP = SOURCES + [("experiments/block_body.hip", UNROLL), ("experiments/gemm_xs.hip", UNROLL), ("experiments/gemm_chain.hip", UNROLL),
-                         ("experiments/resident.hip", UNROLL)]
+                         ("experiments/resident.hip", UNROLL), ("experiments/attn_tail_variants.hip", UNROLL),
+                         ("experiments/pair_norm_variants.hip", UNROLL), ("experiments/pp_stage.hip", UNROLL)]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-I", CSRC]
 
@@ -142,8 +143,9 @@ def _build_one(lib, sources, objdir, defines, lint, force, verbose):
         if force or _newer(s, o) or any(_newer(d, o) for d in deps):
             jobs.append((s, extra, o))
         objs.append(o)
-    # the translation units compile concurrently (hipcc is single-threaded per file; gemm_gx.hip and gemm_ring.hip are the long
-    # poles); at most 16 at a time: os.cpu_count() reports the machine's CPUs, not what a job on a shared machine may use
+    # the translation units compile concurrently (hipcc is single-threaded per file; gemm_gx.hip -- the generated-X GEMM's 16
+    # instantiations alone, since sa_chain.hip and pair_norm.hip compile beside it -- and gemm_ring.hip are the long poles, about
+    # 3 : 2, every other unit under half of gemm_ring.hip); at most 16 at a time: os.cpu_count() reports the machine's CPUs, not what a job on a shared machine may use
     if jobs:
         with ThreadPoolExecutor(max_workers=min(len(jobs), 16, os.cpu_count() or 1)) as ex:
             for f in [ex.submit(_compile, s, extra, o, defines, lint, verbose) for s, extra, o in jobs]:

@@ -1,7 +1,8 @@
 // engine.hip -- the op dispatcher and the runtime API of the fused latent-DDPM denoiser for gfx950 (C-ABI:
 // include/slide_engine.h), with the small per-step kernels (prep / assemble / finalize / t-embedding / condition / DDPM update /
-// transpose / NCHW GroupNorm).  The GEMM kernels are in gemm_ring.hip, gemm_gx.hip and gemm_gxs.hip, the fused attention tails
-// in attn_tail.hip; what crosses translation units is declared in launch.h.
+// transpose / NCHW GroupNorm).  The GEMM kernels are in gemm_ring.hip, gemm_gx.hip, gemm_gxs.hip and sa_chain.hip, the
+// pair-table pass in pair_norm.hip, the fused attention tails in attn_tail.hip and attn_tail_split.hip; what crosses translation
+// units is declared in launch.h, which is also the map of which file defines what.
 #include "gemm_common.h"
 #include "ddpm_update.h"
 #include "launch.h"
@@ -809,7 +810,11 @@ int run_op(const SlideOp &o, hipStream_t s) {
     case SLIDE_OP_PAIR_NORM:
       return slide_launch_pair_norm(o, s);
     case SLIDE_OP_PP_STAGE:
+#ifdef SLIDE_EXPERIMENTS
       return slide_launch_pp_stage(o, s);
+#else
+      return SLIDE_ST_EXPERIMENT;  // (measured slower, opt-in: experiments/pp_stage.hip)
+#endif
     case SLIDE_OP_PAIR_FIRST:
       return slide_launch_pair_first(o, s);
     case SLIDE_OP_SA_CHAIN:

@@ -16,6 +16,22 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
+// split mode: x = hi + 2^-11 lo, hi = fp16(x), lo = fp16(2^11 (x - hi)) -- the scaling keeps lo a NORMAL fp16 number
+// whatever the magnitude of x (unscaled, the low parts of values below ~0.1 would fall into fp16's denormal range)
+__device__ __forceinline__ void split4(const float4 v, f16x4 &hi, f16x4 &lo) {
+  hi = f16x4{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
+  lo = f16x4{(_Float16)((v.x - (float)hi[0]) * 2048.f), (_Float16)((v.y - (float)hi[1]) * 2048.f),
+             (_Float16)((v.z - (float)hi[2]) * 2048.f), (_Float16)((v.w - (float)hi[3]) * 2048.f)};
+}
+// ONE accumulator set for the three products (round 5): the WEIGHT's high term also enters scaled, hs = 2^11 hi (exact in fp16 while
+// |w| < 32 -- the plan checks its weights), so   2^11 (w x) = hs xh + hi xl' + wl' xh   (xl', wl' the scaled low terms) accumulates
+// in one fp32 register set and a final exact 2^-11 restores the scale: the cross products sit 2^-11 below the leading one and keep 13
+// of their own bits in the fp32 sum -- 2^-24 of the total, as with two sets -- at half the accumulator registers.
+__device__ __forceinline__ void gxs_split4w(const float4 v, f16x4 &hi, f16x4 &hs, f16x4 &lo) {
+  split4(v, hi, lo);
+  hs = hi * f16x4{(_Float16)2048.f, (_Float16)2048.f, (_Float16)2048.f, (_Float16)2048.f};
+}
+
 struct GemmArgs {
   const void *X;
   const void *W;
@@ -151,6 +167,11 @@ __device__ __forceinline__ void gstore4(GLOBAL_AS _Float16 *p, float4 v) {
 // the first by this toolchain when both fed conversions (residual path), silently corrupting quads 2p+1.
 __device__ __forceinline__ void lane32_swap(uint32_t &a, uint32_t &b) {
   asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
+}
+__device__ __forceinline__ float other_half(float x) {  // value of lane ^ 32
+  uint32_t a = __float_as_uint(x), b = a;
+  lane32_swap(a, b);  // a = [x.lo | x.lo in the upper lanes], b = [x.hi in the lower lanes | x.hi]
+  return __uint_as_float((threadIdx.x & 32) ? a : b);
 }
 
 template <typename T> __device__ __forceinline__ float4 load4(const T *p);

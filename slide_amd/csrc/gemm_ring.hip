@@ -102,13 +102,6 @@ __global__ __launch_bounds__(256, (PREC == SLIDE_PREC_SPLIT && NPXL == 4) ? 1 : 
                                  : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   };
-  // split mode: x = hi + 2^-11 lo, hi = fp16(x), lo = fp16(2^11 (x - hi)) -- the scaling keeps lo a NORMAL fp16 number
-  // whatever the magnitude of x (unscaled, the low parts of values below ~0.1 would fall into fp16's denormal range)
-  auto split4 = [](const float4 v, f16x4 &hi, f16x4 &lo) {
-    hi = f16x4{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-    lo = f16x4{(_Float16)((v.x - (float)hi[0]) * 2048.f), (_Float16)((v.y - (float)hi[1]) * 2048.f),
-               (_Float16)((v.z - (float)hi[2]) * 2048.f), (_Float16)((v.w - (float)hi[3]) * 2048.f)};
-  };
   const float *aff_lds = nullptr;  // set below (behind the epilogue tables)
   auto store_chunk = [&](int s, int kc) {
     TS *Xs = sbase + s * STAGE;
@@ -313,11 +306,6 @@ __global__ __launch_bounds__(256, 3) void gemm_split_small_kernel(GemmArgs a) {
       wr[p] = gco < a.n_cob * 32 ? *reinterpret_cast<const float4 *>(W + (size_t)gco * a.k_pad + kc * BK + l_c)
                                  : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-  };
-  auto split4 = [](const float4 v, f16x4 &hi, f16x4 &lo) {
-    hi = f16x4{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-    lo = f16x4{(_Float16)((v.x - (float)hi[0]) * 2048.f), (_Float16)((v.y - (float)hi[1]) * 2048.f),
-               (_Float16)((v.z - (float)hi[2]) * 2048.f), (_Float16)((v.w - (float)hi[3]) * 2048.f)};
   };
   const float *aff_lds = nullptr;  // consumer-side affine: the tile's samples' [scale | shift][k_pad], staged once (set below)
   auto store_chunk = [&](int s, int kc, const float4 (&xr)[2], const float4 (&wr)[2]) __attribute__((always_inline)) {

@@ -1,5 +1,5 @@
 // gemm_small.h -- the split-K small-launch GEMM body (16 rows per sample), shared by gemm_ring.hip (gemm_small_kernel,
-// pair_first_kernel) and gemm_gx.hip (sa_chain_p_kernel: the per-point query GEMM of an SA block riding on the launch of its
+// pair_first_kernel) and sa_chain.hip (sa_chain_p_kernel: the per-point query GEMM of an SA block riding on the launch of its
 // fused Mlp chain).  Anonymous namespace: every translation unit gets its own copy.
 #pragma once
 #include "gemm_common.h"
@@ -260,7 +260,7 @@ __device__ __forceinline__ void small_body(const GemmArgs &a, const PairArgs &pa
     gemm_epilogue<SLIDE_PREC_F16, NPXL, 1, 1>(a, one, row0 + rb * 32, cob0 + cb, 0, half, col, epi_lds + cb * EPI_DW,
                                               vec_lds + cb * 96, nullptr);
   if constexpr (PAIR != 0) {
-    // ---- pair-table epilogue (the arithmetic of pair_norm_kernel, gemm_gx.hip, on the accumulators instead of a stored y).
+    // ---- pair-table epilogue (the arithmetic of pair_norm_kernel, experiments/pair_norm_variants.hip, on the accumulators instead of a stored y).
     // The wave's block D[channel][row] is transposed through LDS so that a lane owns ONE channel of ONE of the block's two
     // samples and its registers run over the sample's 16 points.
     __syncthreads();  // every wave has summed its block: the partial-sum area is free

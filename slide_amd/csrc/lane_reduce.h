@@ -123,7 +123,7 @@ __device__ __forceinline__ void lane_row_pair_sums(float *w) {
 }
 
 // ONE level on the N values a lane holds at it: w[0 .. N) -> w[0 .. max(N / 2, 1)).  A caller that forms its values in batches
-// runs the first levels per batch, so that few values are live at a time (the SA chain's statistics, gemm_gx.hip), and the
+// runs the first levels per batch, so that few values are live at a time (the SA chain's statistics, sa_chain.hip), and the
 // later levels on what the batches leave; the value numbering is that of running every level on all values at once.
 template <int LEVEL, int N>
 __device__ __forceinline__ void lane_sum_level(float *w, int lane) {

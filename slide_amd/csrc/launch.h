@@ -12,30 +12,32 @@ struct GemmArgs;  // gemm_common.h
 // Status of an op whose kernel only exists in the EXPERIMENTS build (slide_amd/build.py: libslide_hip_exp.so, -DSLIDE_EXPERIMENTS):
 // the opt-in variants that lost their A/Bs (X-stationary tiles, per-point layer chains, head + update launch, wide / eight-wave
 // attention tails, 128- / 32-channel and 64-deep ring tiles, the round-2 plan's gathered first layers, the register-staged fp16
-// GEMM).  The product library carries only what a default plan dispatches.
+// GEMM, the per-point stage, the pair-table pass on fp16 tables).  The product library carries only what a default plan dispatches.
 #define SLIDE_ST_EXPERIMENT (-20)
 
 // gemm_ring.hip: SLIDE_OP_GEMM, SLIDE_OP_PAIR_FIRST, SLIDE_OP_GEMM_ATTEND
 int slide_launch_gemm(const SlideOp &o, hipStream_t s);
 int slide_launch_pair_first(const SlideOp &o, hipStream_t s);
 int slide_launch_gemm_attend(const SlideOp &o, hipStream_t s);
-// attn_tail.hip: the fused attention tails (fp16)
+// attn_tail.hip: the fused attention tails (fp16): register-X and ring form (argument block: attn_tail.h)
 int slide_launch_attn_tail(const SlideOp &o, hipStream_t s);
+// attn_tail_split.hip: the fused attention tail in split arithmetic (float rows)
+int slide_launch_attn_tail_split(const SlideOp &o, hipStream_t s);
 // rows_ops.hip: the row-major ops of the module path
 int slide_launch_rows_op(const SlideOp &o, hipStream_t s);
 // point_chain.hip
 int slide_launch_point_chain(const SlideOp &o, hipStream_t s);
-// gemm_gx.hip: generated-X GEMM and the per-point table normalisation of the pair decomposition
+// gemm_gx.hip: generated-X GEMM of the pair decomposition (fp16 tables)
 int slide_launch_gemm_gx(const SlideOp &o, hipStream_t s);
 int slide_launch_gemm_gx_dual(const SlideOp &o, hipStream_t s);
-int slide_launch_pair_norm(const SlideOp &o, hipStream_t s);
-int slide_launch_sa_chain(const SlideOp &o, hipStream_t s);
-int slide_launch_sa_chain_p(const SlideOp &o, hipStream_t s);
-// gemm_gxs.hip: the same in split arithmetic (float tables), the split attention tail, the per-point MFMA stages
+// gemm_gxs.hip: the same in split arithmetic (float tables)
 int slide_launch_gemm_gxs(const SlideOp &o, hipStream_t s);
 int slide_launch_gemm_gxs_dual(const SlideOp *pr, hipStream_t s);
-int slide_launch_attn_tail_split(const SlideOp &o, hipStream_t s);
-int slide_launch_pp_stage(const SlideOp &o, hipStream_t s);
+// pair_norm.hip: the pair-table pass as a launch of its own (float tables; device body: pair_norm.h)
+int slide_launch_pair_norm(const SlideOp &o, hipStream_t s);
+// sa_chain.hip: the fused Mlp chain of an SA block, alone and with the attention's per-point query GEMM
+int slide_launch_sa_chain(const SlideOp &o, hipStream_t s);
+int slide_launch_sa_chain_p(const SlideOp &o, hipStream_t s);
 // experiments/block_body.hip (called in the experiments build only)
 int slide_launch_block_body(const SlideOp &o, hipStream_t s);
 #ifdef SLIDE_EXPERIMENTS
@@ -43,6 +45,14 @@ int slide_launch_block_body(const SlideOp &o, hipStream_t s);
 int slide_launch_gemm_xs(const GemmArgs &a, int npxl, int cbw, bool aff, bool gat, int want_occ, hipStream_t s);
 // experiments/gemm_chain.hip
 int slide_launch_gemm_chain(const SlideOp &o, hipStream_t s);
+// experiments/pp_stage.hip: the per-point stage of the split position plan
+int slide_launch_pp_stage(const SlideOp &o, hipStream_t s);
+// experiments/pair_norm_variants.hip: the pair-table pass on fp16 tables (every SLIDE_OP_PAIR_NORM that pair_norm.hip does not run)
+int slide_launch_pair_norm_variants(const SlideOp &o, hipStream_t s);
+// experiments/attn_tail_variants.hip: eight-wave (tail8_on) and wide tails; attn_tail.hip offers every op to it first and goes
+// on with its own forms when the answer is SLIDE_ST_NOT_A_VARIANT
+#define SLIDE_ST_NOT_A_VARIANT (-21)
+int slide_launch_attn_tail_variants(const SlideOp &o, bool tail8_on, hipStream_t s);
 #endif
 
 // hipFuncSetAttribute is per device: the "already raised the dynamic-LDS limit" flags are kept per device so that one

@@ -1,5 +1,6 @@
 // pair_norm.h -- the pair-table pass of the pair decomposition (SLIDE_OP_PAIR_NORM version 2) as a device body
-// shared by gemm_gx.hip (its own launch) and gemm_gxs.hip (a step of the per-point stage kernel of the split plans).
+// shared by its own launch (pair_norm2_kernel below: pair_norm.hip, experiments/pair_norm_variants.hip) and by a step of the
+// per-point stage kernel of the split plans (experiments/pp_stage.hip).
 #pragma once
 #include "gemm_common.h"
 
@@ -11,7 +12,7 @@ namespace {
 // shift for the query GEMM and the generated-X key GEMM -- instead of inside the next launch's prologue.
 // TT = float (round 5): the tables of the SPLIT-arithmetic plans (fp32-grade position DDPM) -- same pass, tables kept in fp32
 // (device body: sample b, nthr threads of the workgroup, dyn_l = [16][NT + 1] floats of LDS for the FP form; called by
-//  pair_norm2_kernel and by the per-point stage kernel of the split plans, gemm_gxs.hip)
+//  pair_norm2_kernel and by the per-point stage kernel of the split plans, experiments/pp_stage.hip)
 template <bool FP, typename TT, int NT>
 __device__ __forceinline__ void pair_norm2_body(int ld, const float *__restrict__ y, const float *__restrict__ xyz,
                                                 const float *__restrict__ wa, const float *__restrict__ wb,
@@ -142,6 +143,19 @@ __device__ __forceinline__ void pair_norm2_body(int ld, const float *__restrict_
     f.scale[(size_t)b * f.bs + c] = sc;
     f.shift[(size_t)b * f.bs + c] = sh;
   }
+}
+
+// the pass as a launch of its own: instantiated with float tables by pair_norm.hip, with fp16 ones by experiments/pair_norm_variants.hip
+template <bool FP, typename TT = _Float16, int NT = 1024>
+__global__ __launch_bounds__(NT) void pair_norm2_kernel(int ld, const float *__restrict__ y, const float *__restrict__ xyz,
+                                                          const float *__restrict__ wa, const float *__restrict__ wb,
+                                                          const SlideEpi *__restrict__ epi, TT *__restrict__ ta,
+                                                          TT *__restrict__ tb, const int *__restrict__ nbr,
+                                                          const float *__restrict__ d2t, const float *__restrict__ wt,
+                                                          const float *__restrict__ vv_in, float *__restrict__ vv_out,
+                                                          const SlideGnFin *__restrict__ finp) {
+  extern __shared__ __attribute__((aligned(16))) float dyn_l[];  // FP: a-values [16][NT + 1]
+  pair_norm2_body<FP, TT, NT>(ld, y, xyz, wa, wb, epi, ta, tb, nbr, d2t, wt, vv_in, vv_out, finp, blockIdx.x, blockDim.x, dyn_l);
 }
 
 }  // namespace

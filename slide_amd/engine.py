@@ -798,7 +798,7 @@ class DenoiserEngine:
                     and l2.gs in (4, 8, 16) and l3.gs in (4, 8, 16))
 
     def _sa_chain(self, pfx, npx_log2, pair, cvec, seg, final_out, final_coff):
-        """second_mlp -> rest_mlp of an SA block as ONE launch (SLIDE_OP_SA_CHAIN, csrc/gemm_gx.hip: h2 stays in registers).
+        """second_mlp -> rest_mlp of an SA block as ONE launch (SLIDE_OP_SA_CHAIN, csrc/sa_chain.hip: h2 stays in registers).
         Returns False when the shapes are outside what the kernel covers (the two-launch path then runs)."""
         sd, B = self.sd, self.B
         if pair["vv"] is not None or not self._sa_chain_shapes(pfx, npx_log2):
@@ -1219,7 +1219,7 @@ class DenoiserEngine:
             if (self.prec == 1 and self.use_glds and self.knobs.SLIDE_ATTN_TAIL and vlay.unpermuted):
                 self._lane = 0
                 return ("fused", u, lay)  # scores are computed inside the fused attention tail (finish)
-            # round 5: the same tail in the split arithmetic on float rows (csrc/gemm_gxs.hip attn_tail_split_kernel;
+            # round 5: the same tail in the split arithmetic on float rows (csrc/attn_tail_split.hip attn_tail_split_kernel;
             # SLIDE_TAIL_SPLIT=0: scores GEMM + values GEMM + combine launch).  Its single-accumulator split needs |w| < 32.
             if (self.use_gxs and self.knobs.SLIDE_TAIL_SPLIT and vlay.unpermuted
                     and self._split1_ok(self._w(apfx + ".weight_conv.5.weight"), self._w(apfx + ".feat_out_conv.0.weight"))):
@@ -1240,7 +1240,7 @@ class DenoiserEngine:
         return (finish_scores, finish), cout
 
     def _attn_tail(self, apfx, npx_log2, u, lay, mo, out):
-        """the fused end of an AttentionModule as ONE launch (SLIDE_OP_ATTN_TAIL: csrc/attn_tail.hip in fp16, csrc/gemm_gxs.hip in the
+        """the fused end of an AttentionModule as ONE launch (SLIDE_OP_ATTN_TAIL: csrc/attn_tail.hip in fp16, csrc/attn_tail_split.hip in the
         split arithmetic): scores W5 . u + b5 (u: the intermediate layer's output in its PADDED GroupNorm layout `lay`), values
         relu(GN(Wv . mo + bv)), out[point] = sum_k softmax_k(scores) * values.  Returns the launch"""
         cout = self.sd[apfx + ".weight_conv.5.weight"].shape[0]
@@ -1731,7 +1731,7 @@ class DenoiserEngine:
 
     def _merge_pp(self):
         """split plans (round 5): runs of consecutive per-point launches -- 16-row SLIDE_OP_GEMM in the split arithmetic and the float
-        pair-table pass -- become ONE SLIDE_OP_PP_STAGE launch each (csrc/gemm_gxs.hip: one workgroup per sample walks the steps, the
+        pair-table pass -- become ONE SLIDE_OP_PP_STAGE launch each (csrc/experiments/pp_stage.hip: one workgroup per sample walks the steps, the
         dense layers as exact fp32 FMA chains; 30 -> 17 launches per position step).  SLIDE_PP=0 keeps the launches apart."""
         # OPT-IN (SLIDE_PP=1): measured SLOWER -- one workgroup per sample re-reads every layer's weights per sample and its K loop is a
         # chain of dependent L2 round trips on four waves: 55 - 131 us per stage launch against 27 - 45 us for the launches it replaces

@@ -45,7 +45,7 @@ BOUND, elementwise, against the UNROUNDED float64 result (u = 2^-24, H = 2^-11):
                      + R (sum_k w_k |v_k| ds_k + W sum_j w_j ds_j)                               (score uncertainty, first order)
                      + sum_k w_k dv_k                                                            (value uncertainty)
                  R = exp(2 max ds) covers the remainder of the first-order expansion (ds is 1e-3 at most in the fused cases).
-  reciprocal     v_rcp_f32 in place of the division: 1 ulp (csrc/gemm_gxs.hip: "v_rcp instead of an IEEE division (1 ulp)") = 2 u |out|,
+  reciprocal     v_rcp_f32 in place of the division: 1 ulp (csrc/attn_tail_split.hip: "v_rcp instead of an IEEE division (1 ulp)") = 2 u |out|,
                  taken as 2 u W.  rows_cases' count already holds 3 u for 1 / l; both are kept.
   underflow      the max slot contributes e = 1 exactly, so den >= 1: a weight that underflows (or is flushed) costs at most 2^-126 |v|
                  absolute, nothing relative -- not a term.
@@ -201,7 +201,7 @@ def layout(C):
 
 
 def dispatch(i, f1, tail_rx=True):
-    """the kernel run_attn_tail / slide_launch_attn_tail_split (csrc/attn_tail.hip, csrc/gemm_gxs.hip) picks for an op's i[] and f[1] in
+    """the kernel run_attn_tail / slide_launch_attn_tail_split (csrc/attn_tail.hip, csrc/attn_tail_split.hip) picks for an op's i[] and f[1] in
     the product build, or its status"""
     f1 = int(f1)
     rows, x1_ld, k1, x2_ld, k2, n_cob, npxl = i[:7]
