@@ -118,9 +118,99 @@ class InAffine(NamedTuple):
     bs: int
 
 
+class GxArgs(NamedTuple):
+    """the generated input of a SLIDE_OP_GEMM_GX launch (_emit_gx): columns [coff, coff + k_pad) of the pair tables, never stored"""
+    ta: torch.Tensor          # tables [B*16][t_ld]: fp16, split plans float
+    tb: torch.Tensor
+    coff: int
+    k_pad: int
+    rows: int
+    mode: int                 # 0: a first Mlp layer's output (+ add), 1: the keys under the joint GroupNorm (in_affine)
+    add: AddVec = None
+    vv: torch.Tensor = None   # per-sample (vd | vw) fp32 [B][2][t_ld] of the 8-neighbour samples
+
+
+class PairTables(NamedTuple):
+    """what _pair_first leaves for the consumers (generated-X GEMMs, PAIR residuals): the tables and their geometry"""
+    ta: torch.Tensor
+    tb: torch.Tensor
+    ldy: int
+    offs: list                # first table column of every segment
+    rows: int                 # K-expanded rows
+    vv: torch.Tensor          # per-sample (vd | vw) [B][2][ldy], 8-neighbour samples (else None)
+    vv_in: np.ndarray         # their coefficient rows [2][ldy] on the host
+    tabs: tuple               # (neighbour, d2, w) tables of the 8-neighbour samples (else None)
+
+    def __getitem__(self, k):  # (fields by name as well, as callers read the dict this record replaced)
+        return getattr(self, k) if isinstance(k, str) else tuple.__getitem__(self, k)
+
+
+class PairFused(NamedTuple):
+    """what SLIDE_OP_PAIR_FIRST takes beside its per-point GEMM (_emit_pair_first): the table pass of _pair_first"""
+    cob0: int                 # 32-channel blocks of the leading (non-pair) segments
+    K: int
+    wa: torch.Tensor          # coordinate weights [ldy][4] of the a / b tables; vv_in [2][ldy]: 8-neighbour samples (else None)
+    wb: torch.Tensor
+    vv_in: torch.Tensor
+    t: PairTables             # what the pass writes
+
+
+class BlockPair(NamedTuple):
+    """an SA / FP block's view of its pair tables: [first_mlp | res_connect | keys] at columns off1 / offr / offk"""
+    t: PairTables
+    off1: int
+    offr: int
+    offk: int
+    lay1: GnLayout            # first_mlp's output layout
+    add1: AddVec              # its t-embedding rows, added by the consumers (or None)
+    rvv: torch.Tensor         # (vd | vw) of the res_connect columns [2][rres], 8-neighbour samples (else None)
+
+
+class Query(NamedTuple):
+    """an attention block's per-point query branch (_attention_query): its buffers and its GEMM segment"""
+    Tq: torch.Tensor
+    ssum: torch.Tensor
+    ssq: torch.Tensor
+    qseg: dict
+
+
+class AttnState(NamedTuple):
+    """an attention block between its three phases (_attn_open -> _attn_scores -> _attn_finish)"""
+    apfx: str
+    npx_log2: int
+    C1: int                   # query channels; C1p / C2p: padded query / key channels, ldT = C1p + C2p
+    C1p: int
+    C2p: int
+    ldT: int
+    cout: int
+    Tq: torch.Tensor          # per-point queries; their statistics and the keys' are in `fin`
+    Tk: torch.Tensor          # stored keys (None: generated from the pair tables)
+    scale: torch.Tensor       # joint GroupNorm of [q | k] as a per-sample affine ...
+    shift: torch.Tensor
+    fin: SlideGnFin           # ... and what finalises it (host copy: statistics, group tables, gamma / beta, scale / shift)
+    pair_fin: bool            # the pair-table pass finalised it
+    pair: BlockPair           # (None: stored first-layer outputs)
+    mo: torch.Tensor          # the values' input, written between scores and finish
+    end: str                  # "body" (SLIDE_OP_BLOCK_BODY takes over after P) | "fused" (one tail launch) | "combine"
+    P: torch.Tensor = None    # from _attn_scores: per-point query half of weight_conv.2, u and its layout, scores (end == "combine")
+    u: torch.Tensor = None
+    lay: GnLayout = None
+    S: torch.Tensor = None
+
+
+class ChainFront(NamedTuple):
+    """the last FP block's second Mlp as _point_chain may chain it to the head"""
+    launches: list
+    Z: torch.Tensor
+    zin: int
+    m2: str
+    n1: int
+    n2: int
+
+
 def _rec(T, v):
-    """a plain tuple (or None) as the record T"""
-    return None if v is None else T(*v)
+    """a plain tuple, or a dict of its fields, (or None) as the record T"""
+    return None if v is None else T(**v) if isinstance(v, dict) else T(*v)
 
 
 _SEG_RECORDS = dict(layout=GnLayout, addvec=AddVec, pre_add=PreAdd, res_pair=ResPair, stats=Stats)
@@ -538,18 +628,16 @@ class DenoiserEngine:
         return _Layer(segs, widths, W, Wd, w_cm, ed, edp, W.shape[0] // 32, ld, rows, 2 * rows * sum(int(sg["w"].size) for sg in segs))
 
     def _gemm(self, X, npx_log2, segs, in_cols=None, in_affine=None, gather=None, gn_fin=None,
-              pre_gather=None, gx=None, pair_tabs=None, pair_fused=None, defer=None, chain=None):
+              pre_gather=None, gx=None, pair_tabs=None, pair_fused=None, chain=None):
         """X: input buffer [rows][ld].  segs: list of dicts describing consecutive output segments:
              w (O,I) bias (O) | out (tensor) out_coff | mode flags | gn=(gamma,beta) for NORM | layout (gn_layout) |
              addvec (AddVec) | residual tensor | res_pair (ResPair) | pre_add (PreAdd) | stats (Stats)
            in_cols: physical column index of every logical input channel (None = identity).
-           in_affine (InAffine), gather (Gather): X holds the columns that are not gathered."""
-        in_affine, gather = _rec(InAffine, in_affine), _rec(Gather, gather)
-        if defer is not None:  # a layer CHAINED onto a split generated-X GEMM (csrc/gemm_gxs.hip): packed, not launched
-            rows, ld = defer["rows"], defer["k_pad"]
-            assert X is None and self.use_gxs and gather is None and gn_fin is None and gx is None and in_affine is None
-        elif gx is not None:  # generated-X GEMM of the pair decomposition (SLIDE_OP_GEMM_GX): X is never stored
-            rows, ld = gx["rows"], gx["k_pad"]
+           in_affine (InAffine), gather (Gather): X holds the columns that are not gathered.
+           gx (GxArgs), pair_fused (PairFused), chain (_chained_layer): the launch's other forms."""
+        in_affine, gather, gx = _rec(InAffine, in_affine), _rec(Gather, gather), _rec(GxArgs, gx)
+        if gx is not None:  # generated-X GEMM of the pair decomposition (SLIDE_OP_GEMM_GX): X is never stored
+            rows, ld = gx.rows, gx.k_pad
             assert X is None and gather is None and gn_fin is None and npx_log2 in (7, 8) and (self.use_cm or self.use_gxs)
         else:
             rows, ld = X.shape
@@ -561,8 +649,6 @@ class DenoiserEngine:
         # split-K small-launch kernel, which reads row-major weights)
         w_cm = bool(self.use_cm and npx_log2 >= 7) or (gx is not None and self.prec == 1)
         L = self._pack_layer(segs, npx_log2, rows, ld, in_cols, w_cm, chain=chain, pair_tabs=pair_tabs, pre_gather=pre_gather)
-        if defer is not None:
-            return dict(W=L.Wd, epi=L.epi, epi_ptr=L.epi_ptr, n_cob=L.n_cob, k_pad=ld, flops=L.flops, wr=L.written(), wbytes=L.W.size * 4)
         if gx is not None:
             return self._emit_gx(L, gx, npx_log2, in_affine, pair_tabs, chain)
         if pair_fused is not None:
@@ -570,18 +656,22 @@ class DenoiserEngine:
             return self._emit_pair_first(L, X, npx_log2, pair_fused)
         return self._emit_plain(L, X, npx_log2, in_affine, gather, gn_fin, pre_gather, pair_tabs)
 
+    def _chained_layer(self, seg, npx_log2, rows, k_pad, pair_tabs=None):
+        """a layer CHAINED onto a split generated-X GEMM (csrc/gemm_gxs.hip): packed (_Layer), not launched -- _gemm(chain=) takes it"""
+        assert self.use_gxs
+        return self._pack_layer([seg], npx_log2, rows, k_pad, None, bool(self.use_cm and npx_log2 >= 7), pair_tabs=pair_tabs)
+
     def _emit_pair_first(self, L, X, npx_log2, pf):
         """SLIDE_OP_PAIR_FIRST: per-point GEMM + pair-table pass in one launch (_pair_first)"""
-        rows, ld = L.rows, L.ld
+        rows, ld, t = L.rows, L.ld, pf.t
         assert npx_log2 == 4 and self.prec == 1 and not L.w_cm
         assert X.dtype == self.adt and not self._is_cm(X)
         self.flops += L.flops
-        return self._emit(make_op(OP_PAIR_FIRST, i=(rows, self._ldp(X), ld, L.n_cob, pf["cob0"], pf["ld"], pf["K"]),
-                                  p=(X.data_ptr(), L.Wd.data_ptr(), L.epi_ptr, self.xyz.data_ptr(), pf["wa"].data_ptr(),
-                                     pf["wb"].data_ptr(), pf["ta"].data_ptr(), pf["tb"].data_ptr(), _dp(pf.get("nbr")),
-                                     _dp(pf.get("d2")), _dp(pf.get("w")), _dp(pf.get("vv_in")), _dp(pf.get("vv")))),
-                          flops=L.flops, nbytes=(rows * ld * 2 + L.W.size * 2, 2 * rows * pf["ld"] * 2 + rows * 32 * pf["cob0"] * 2),
-                          name="pair_first_kernel<%s>" % ("true" if pf["K"] == 8 else "false"))
+        return self._emit(make_op(OP_PAIR_FIRST, i=(rows, self._ldp(X), ld, L.n_cob, pf.cob0, t.ldy, pf.K),
+                                  p=(X.data_ptr(), L.Wd.data_ptr(), L.epi_ptr, self.xyz.data_ptr(), pf.wa.data_ptr(), pf.wb.data_ptr(),
+                                     t.ta.data_ptr(), t.tb.data_ptr(), *map(_dp, t.tabs or (None,) * 3), _dp(pf.vv_in), _dp(t.vv))),
+                          flops=L.flops, nbytes=(rows * ld * 2 + L.W.size * 2, 2 * rows * t.ldy * 2 + rows * 32 * pf.cob0 * 2),
+                          name="pair_first_kernel<%s>" % ("true" if pf.K == 8 else "false"))
 
     def _emit_plain(self, L, X, npx_log2, in_affine, gather, gn_fin, pre_gather, pair_tabs):
         """SLIDE_OP_GEMM over a stored X (csrc/gemm_ring.hip run_gemm)"""
@@ -656,30 +746,25 @@ class DenoiserEngine:
         return all(float(np.abs(w).max()) < 31.0 for w in ws if w.size)
 
     def _emit_gx(self, L, gx, npx_log2, in_affine, pair_tabs, chain=None):
-        """SLIDE_OP_GEMM_GX (include/slide_engine.h): gx = dict(ta, tb (fp16 tables [B*16][t_ld]), coff (first table column),
-        k_pad, rows, mode, add (AddVec) or None, vv = per-sample (vd | vw) fp32 [B][2][t_ld] of the 8-neighbour samples or None);
-        pair_tabs = (neighbour, d2, w tables) for those"""
+        """SLIDE_OP_GEMM_GX (include/slide_engine.h) of the input `gx` (GxArgs); pair_tabs = (neighbour, d2, w tables) of the 8-neighbour
+        samples; chain: the layer that consumes this one's output in the same launch (_chained_layer)"""
         rows, ld, n_cob = L.rows, L.ld, L.n_cob
-        ta, tb, coff = gx["ta"], gx["tb"], gx["coff"]
+        ta, tb, coff, add, vv = gx.ta, gx.tb, gx.coff, _rec(AddVec, gx.add), gx.vv
         tes = ta.element_size()
         assert ta.dtype == (torch.float16 if self.prec == 1 else torch.float32) and ta.shape == tb.shape and coff % 8 == 0
         assert ta.shape[1] >= coff + ld
-        fl = L.flops
-        rd = 2 * (rows >> npx_log2) * 16 * ld * tes + L.W.size * tes
-        wr = L.written()
+        fl, rd, wr = L.flops, 2 * (rows >> npx_log2) * 16 * ld * tes + L.W.size * tes, L.written()
         if chain is not None:  # the chained layer's work rides on this launch
-            fl += chain["flops"]; rd += chain["wbytes"]; wr += chain["wr"]
-        add = _rec(AddVec, gx.get("add"))
-        vv = gx.get("vv")
+            fl += chain.flops; rd += chain.W.size * 4; wr += chain.written()
         assert (npx_log2 == 7) == (pair_tabs is not None)
         # (the launcher's choice, csrc/gemm_gx.hip: mode-1 layers run 256 x 64 tiles when three workgroups fit a CU's LDS)
-        nsamp, nvec = 256 >> npx_log2, (2 if gx["mode"] else 1) + (2 if npx_log2 == 7 else 0)
+        nsamp, nvec = 256 >> npx_log2, (2 if gx.mode else 1) + (2 if npx_log2 == 7 else 0)
         # (LDS of the 64-channel form: ring stages of 8 KB of weights + 4 KB of streamed table images per sample, epilogue
         #  descriptors, per-sample vectors; three stages, else two)
         shm64 = lambda nst: nst * (8192 + 4096 * nsamp) + (2 * 40 + 2 * 96) * 4 + nsamp * nvec * ld * 2 + 16
         knob = self.knobs.SLIDE_GX_N64
         n64, nst = 0, 3
-        if knob != "0" and gx["mode"] == 1 and shm64(3) <= 53 * 1024:
+        if knob != "0" and gx.mode == 1 and shm64(3) <= 53 * 1024:
             n64 = 1
         elif knob != "0" and self.knobs.SLIDE_GX_N64W and (
                 n_cob <= 2 or ((rows + 255) // 256) * ((n_cob + 3) // 4) <= 256):
@@ -691,26 +776,26 @@ class DenoiserEngine:
         if n64 == 0:  # 128-channel tiles: two workgroups per CU (80 KB each)
             shm128 = lambda k_: k_ * (16384 + 4096 * nsamp) + (4 * 40 + 4 * 96) * 4 + nsamp * nvec * ld * 2 + 16
             nst = 3 if shm128(3) <= 80 * 1024 else 2
-        name = "gemm_gx_%skernel<%d, %d, %d>" % (("", "n64_", "n64w_")[n64], npx_log2, nst, gx["mode"])
+        name = "gemm_gx_%skernel<%d, %d, %d>" % (("", "n64_", "n64w_")[n64], npx_log2, nst, gx.mode)
         if self.prec == 2:  # split arithmetic on float tables: csrc/gemm_gxs.hip (256 x 64 tiles)
             if not self._split1_ok(L.W):
                 raise SlideHipError("a weight of magnitude >= 31 in a generated-X layer: the split pair-decomposition kernels scale the "
                                     "weights' high terms by 2^11 in fp16 -- build this plan with SLIDE_GXS=0")
             n64 = 3
             name = ("gemm_gxs_chain_kernel<%d>" % npx_log2) if chain is not None else \
-                "gemm_gxs_kernel<%d, %d>" % (npx_log2, gx["mode"])
-            assert chain is None or (npx_log2 == 8 and gx["mode"] == 0 and n_cob <= 2 and chain["k_pad"] == n_cob * 32)
+                "gemm_gxs_kernel<%d, %d>" % (npx_log2, gx.mode)
+            assert chain is None or (npx_log2 == 8 and gx.mode == 0 and n_cob <= 2 and chain.ld == n_cob * 32)
         self.flops += fl
         return self._emit(make_op(OP_GEMM_GX,
-                                  i=(rows, ta.shape[1], ld, n_cob, npx_log2, 0 if in_affine is None else in_affine.bs, gx["mode"],
+                                  i=(rows, ta.shape[1], ld, n_cob, npx_log2, 0 if in_affine is None else in_affine.bs, gx.mode,
                                      0 if add is None else add.bs, 0 if add is None else add.idx_stride, 0 if vv is None else 2 * vv.shape[2]),
-                                  f=(float(n64),) + ((float(chain["n_cob"]), float(chain["k_pad"])) if chain is not None else ()),
+                                  f=(float(n64),) + ((float(chain.n_cob), float(chain.ld)) if chain is not None else ()),
                                   p=self._affine_ptrs(ta.data_ptr() + tes * coff, L.Wd.data_ptr(), L.epi_ptr, in_affine) +
                                     (tb.data_ptr() + tes * coff,
                                      None if add is None else add.vec.data_ptr() + 4 * add.off,
                                      None if add is None else _dp(add.idx)) + tuple(_dp(t) for t in pair_tabs or (None,) * 3) +
                                     (None if vv is None else vv.data_ptr() + 4 * coff,
-                                     None if chain is None else chain["W"].data_ptr(), None if chain is None else chain["epi_ptr"])),
+                                     None if chain is None else chain.Wd.data_ptr(), None if chain is None else chain.epi_ptr)),
                           flops=fl, nbytes=(rd, wr), name=name)
 
     # ------------------------------------------------------------------ blocks
@@ -720,7 +805,7 @@ class DenoiserEngine:
         return dict(w=self._w(conv + ".weight"), bias=sd[conv + ".bias"], mode=EPI_NORM, flags=F_POST_RELU,
                     layout=gn_layout(sd[conv + ".weight"].shape[0]), gn=(sd[gn + ".weight"], sd[gn + ".bias"]), **kw)
 
-    def _mlp_segments(self, pfx, tvec, cvec, out1, res_out):
+    def _mlp_segments(self, pfx, tvec, out1, res_out):
         """first_mlp + res_connect segments of Mlp_plus_t_emb (pointnet2_modules.py:119-176) sharing one input"""
         sd = self.sd
         c1 = sd[pfx + ".first_mlp.0.weight"].shape[0]
@@ -734,55 +819,39 @@ class DenoiserEngine:
 
     def _mlp_tail(self, pfx, npx_log2, h1, cvec, r, final_out, final_coff=0, pair=None):
         """second_mlp (+fc_condition) [+ rest_mlp] + residual, writing the module output.
-        pair (the block's pair decomposition, _pair_first): h1 and r are not buffers -- the first GEMM generates its input
+        pair (BlockPair, the block's pair decomposition): h1 and r are not buffers -- the first GEMM generates its input
         from the pair tables (SLIDE_OP_GEMM_GX mode 0) and the residual enters as a PAIR residual"""
         sd = self.sd
-        rows = h1.shape[0] if pair is None else pair["rows"]
+        t, rows = (None, h1.shape[0]) if pair is None else (pair.t, pair.t.rows)
 
         def first_gemm(seg_, **kw):
             if pair is None:
                 return self._gemm(h1, npx_log2, [seg_])
-            lay1 = pair["lay1"]
-            self._gemm(None, npx_log2, [seg_], in_cols=lay1.index,
-                       gx=dict(ta=pair["ta"], tb=pair["tb"], coff=pair["off1"], k_pad=ru(lay1.width), rows=rows, mode=0,
-                               add=pair["add1"], vv=pair["vv"]), pair_tabs=pair["tabs"], **kw)
+            self._gemm(None, npx_log2, [seg_], in_cols=pair.lay1.index, pair_tabs=t.tabs, **kw,
+                       gx=GxArgs(t.ta, t.tb, pair.off1, ru(pair.lay1.width), rows, 0, pair.add1, t.vv))
 
-        def with_res(seg_):
-            if pair is None:
-                seg_["residual"] = r
-            else:
-                seg_["res_pair"] = ResPair(pair["ta"], pair["tb"], pair["offr"], pair["rvv"])
-            return seg_
-        has_rest = (pfx + ".rest_mlp.0.weight") in sd
+        # the module's last layer writes the output and adds the residual
+        last = dict(out=final_out, out_coff=final_coff, **(dict(residual=r) if pair is None else
+                                                           dict(res_pair=ResPair(t.ta, t.tb, pair.offr, pair.rvv))))
         c2 = sd[pfx + ".second_mlp.0.weight"].shape[0]
         seg = self._conv_gn_relu(pfx + ".second_mlp.0", pfx + ".second_mlp.1.group_norm")
         if (pfx + ".fc_condition.weight") in sd:
             seg["addvec"] = AddVec(cvec, self._cvec_off(pfx + ".fc_condition", c2), self._c_bs)
-        if has_rest and pair is not None and self._sa_chain(pfx, npx_log2, pair, cvec, seg, final_out, final_coff):
+        if (pfx + ".rest_mlp.0.weight") not in sd:
+            return first_gemm(dict(seg, **last))
+        if pair is not None and self._sa_chain(pfx, npx_log2, pair, seg, final_out, final_coff):
             return
-        if has_rest:
-            assert gn_layout(c2).unpermuted, "second_mlp width with padded GroupNorm groups"
-            seg3 = with_res(self._conv_gn_relu(pfx + ".rest_mlp.0", pfx + ".rest_mlp.1.group_norm", out=final_out, out_coff=final_coff))
-        if (has_rest and pair is not None and self.use_gxs and npx_log2 == 8 and ru(gn_layout(c2).width) <= 64
-                and self.knobs.SLIDE_GXS_CHAIN):
+        assert gn_layout(c2).unpermuted, "second_mlp width with padded GroupNorm groups"
+        seg3 = self._conv_gn_relu(pfx + ".rest_mlp.0", pfx + ".rest_mlp.1.group_norm", **last)
+        if (pair is not None and self.use_gxs and npx_log2 == 8 and ru(gn_layout(c2).width) <= 64 and self.knobs.SLIDE_GXS_CHAIN
+                and self._split1_ok(seg3["w"])):
             # split plans (round 5): second_mlp -> rest_mlp of an SA block in ONE launch -- h2 stays in the generated-X kernel's
             # accumulators and feeds rest_mlp's contraction from there (csrc/gemm_gxs.hip, CHAIN); needs every channel of h2 in
             # one 64-channel tile.  SLIDE_GXS_CHAIN=0: two launches and an h2 round trip
-            if self._split1_ok(seg3["w"]):
-                layer2 = self._gemm(None, npx_log2, [seg3], pair_tabs=pair["tabs"], defer=dict(rows=rows, k_pad=ru(c2)))
-                seg["out"] = None
-                first_gemm(seg, chain=layer2)
-                return
-        if has_rest:
-            h2 = self._buf(rows, c2, cm=npx_log2 >= 7)
-            seg["out"] = h2
-            first_gemm(seg)
-            self._gemm(h2, npx_log2, [seg3], pair_tabs=None if pair is None else pair["tabs"])
-        else:
-            with_res(seg)
-            seg["out"] = final_out
-            seg["out_coff"] = final_coff
-            first_gemm(seg)
+            return first_gemm(dict(seg, out=None), chain=self._chained_layer(seg3, npx_log2, rows, ru(c2), t.tabs))
+        h2 = self._buf(rows, c2, cm=npx_log2 >= 7)
+        first_gemm(dict(seg, out=h2))
+        self._gemm(h2, npx_log2, [seg3], pair_tabs=None if pair is None else t.tabs)
 
     def _sa_chain_shapes(self, pfx, npx_log2):
         """does SLIDE_OP_SA_CHAIN cover this Mlp's second_mlp -> rest_mlp (widths, identity GroupNorm layouts, group sizes)?"""
@@ -797,16 +866,15 @@ class DenoiserEngine:
         return bool(c2 in (128, 256) and c3 % 256 == 0 and c1 % 64 == 0 and l1.identity and l2.identity and l3.identity
                     and l2.gs in (4, 8, 16) and l3.gs in (4, 8, 16))
 
-    def _sa_chain(self, pfx, npx_log2, pair, cvec, seg, final_out, final_coff):
-        """second_mlp -> rest_mlp of an SA block as ONE launch (SLIDE_OP_SA_CHAIN, csrc/sa_chain.hip: h2 stays in registers).
-        Returns False when the shapes are outside what the kernel covers (the two-launch path then runs)."""
+    def _sa_chain(self, pfx, npx_log2, pair, seg, final_out, final_coff):
+        """second_mlp -> rest_mlp of an SA block (pair: its BlockPair) as ONE launch (SLIDE_OP_SA_CHAIN, csrc/sa_chain.hip: h2 stays in
+        registers).  Returns False when the shapes are outside what the kernel covers (the two-launch path then runs)."""
         sd, B = self.sd, self.B
-        if pair["vv"] is not None or not self._sa_chain_shapes(pfx, npx_log2):
+        if pair.t.vv is not None or not self._sa_chain_shapes(pfx, npx_log2):
             return False
         w1, w2 = self._w(pfx + ".second_mlp.0.weight"), self._w(pfx + ".rest_mlp.0.weight")
-        c2, c1 = w1.shape
-        c3 = w2.shape[0]
-        lay1, l2, l3 = GnLayout(*pair["lay1"]), gn_layout(c2), gn_layout(c3)
+        (c2, c1), c3 = w1.shape, w2.shape[0]
+        lay1, l2, l3 = pair.lay1, gn_layout(c2), gn_layout(c3)
         assert lay1.unpermuted and len(lay1.index) == c1 and lay1.width == c1
         if not (self._is_cm(final_out) and final_coff == 0 and final_out.shape[1] == c3):
             return False
@@ -815,20 +883,17 @@ class DenoiserEngine:
              self.A.put(epi_vectors(GnLayout.plain(c2), c2, sd[pfx + ".second_mlp.0.bias"], seg["gn"])),
              self.A.put(epi_vectors(GnLayout.plain(c3), c3, sd[pfx + ".rest_mlp.0.bias"],
                                     (sd[pfx + ".rest_mlp.1.group_norm.weight"], sd[pfx + ".rest_mlp.1.group_norm.bias"])))]
-        add0, add1 = _rec(AddVec, pair["add1"]), _rec(AddVec, seg.get("addvec"))
-        ta, tb = pair["ta"], pair["tb"]
-        rows = B * 256
-        fl = 2 * rows * (w1.size + w2.size)
+        add0, add1, ta, tb = pair.add1, _rec(AddVec, seg.get("addvec")), pair.t.ta, pair.t.tb
+        rows, fl = B * 256, 2 * B * 256 * (w1.size + w2.size)
         self.flops += fl
         self._emit(make_op(OP_SA_CHAIN,
                            i=(B, ta.shape[1], c1, c2, c3, l2.gs, l3.gs, 0 if add0 is None else add0.idx_stride,
                               0 if add0 is None else add0.bs, 0 if add1 is None else add1.bs),
                            f=(1.0 / (l2.gs_logical * 256), 1.0 / (l3.gs_logical * 256), 1.0 if self._is_fm(final_out) else 0.0),
-                           p=(ta.data_ptr() + 2 * pair["off1"], tb.data_ptr() + 2 * pair["off1"],
-                              ta.data_ptr() + 2 * pair["offr"], tb.data_ptr() + 2 * pair["offr"],
+                           p=(ta.data_ptr() + 2 * pair.off1, tb.data_ptr() + 2 * pair.off1,
+                              ta.data_ptr() + 2 * pair.offr, tb.data_ptr() + 2 * pair.offr,
                               d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
-                              None if add0 is None else add0.vec.data_ptr() + 4 * add0.off,
-                              None if add0 is None else _dp(add0.idx),
+                              *((None, None) if add0 is None else (add0.vec.data_ptr() + 4 * add0.off, _dp(add0.idx))),
                               None if add1 is None else add1.vec.data_ptr() + 4 * add1.off, final_out.data_ptr())),
                    flops=fl, nbytes=(2 * B * 16 * (c1 + c3) * 2 + (w1.size + w2.size) * 2, rows * c3 * 2),
                    name="sa_chain_kernel<%d>" % (c2 // 32))
@@ -839,14 +904,13 @@ class DenoiserEngine:
         table only, so the query GEMMs of two blocks that read the same table (an SA block and the FP block that takes the
         same features as its skip input) are issued as ONE launch by whichever block comes first"""
         sd, B = self.sd, self.B
-        C1 = sd[apfx + ".feat_conv.weight"].shape[0]
-        C2 = sd[apfx + ".grouped_feat_conv.weight"].shape[0]
-        ldT = ru(C1) + ru(C2)
-        Tq = self.A.zeros(B * 16, ru(C1), dtype=self.adt)
+        C1p = ru(sd[apfx + ".feat_conv.weight"].shape[0])
+        ldT = C1p + ru(sd[apfx + ".grouped_feat_conv.weight"].shape[0])
+        Tq = self.A.zeros(B * 16, C1p, dtype=self.adt)
         ssum, ssq = self.A.zeros(B, ldT), self.A.zeros(B, ldT)
         qseg = dict(w=self._w(apfx + ".feat_conv.weight"), bias=sd[apfx + ".feat_conv.bias"], mode=EPI_STATS,
                     flags=F_PRE_RELU, out=Tq, stats=Stats(ssum, ssq, 0, float(K)))
-        return dict(Tq=Tq, ssum=ssum, ssq=ssq, qseg=qseg)
+        return Query(Tq, ssum, ssq, qseg)
 
     def _pair_first(self, npx_log2, K, feat_in, C, segs, coords, fin=None, lead_segs=()):
         """PAIR DECOMPOSITION of a block's shared first layer (csrc/gemm_gx.hip): the 1x1 convolutions over the grouped input
@@ -855,7 +919,7 @@ class DenoiserEngine:
         SLIDE_OP_PAIR_NORM (tables a, b in fp16 with the GroupNorm of NORM segments folded in, sums of STATS segments);
         the K-expanded outputs are never stored.  segs: the segment dicts of the old shared GEMM (w over all grouped
         channels); coords: dict(rel, abs, ctr = first column of each 3-channel coordinate group, d2 / w = column or None).
-        Returns the context the consumers (generated-X GEMMs, PAIR residuals) take."""
+        Returns the PairTables the consumers (generated-X GEMMs, PAIR residuals) take."""
         B = self.B
         ysegs = []
         offs, ldy = seg_offsets(segs)
@@ -881,14 +945,13 @@ class DenoiserEngine:
             psegs.append(dict({k_: sg[k_] for k_ in ("mode", "flags", "layout", "gn", "stats") if k_ in sg}, w=w[:, :0], out=None))
         assert sum(3 for _ in ("rel", "abs", "ctr")) + (2 if coords.get("d2") is not None else 0) + C == segs[0]["w"].shape[1]
         tdt = torch.float16 if self.prec == 1 else torch.float32  # (split plans: float tables)
-        ta = self.A.zeros(B * 16, ldy, dtype=tdt)
-        tb = self.A.zeros(B * 16, ldy, dtype=tdt)
+        ta, tb = self.A.zeros(B * 16, ldy, dtype=tdt), self.A.zeros(B * 16, ldy, dtype=tdt)
         fp = K == 8
-        d = [self.A.put(wa), self.A.put(wb)]
-        vv = rvv_all = None
+        wa_d, wb_d = self.A.put(wa), self.A.put(wb)
+        tabs = vv_d = vv = None
         if fp:
-            d.append(self.A.put(vv_in))
-            vv = self.A.zeros(B, 2, ldy)
+            tabs, vv_d, vv = (self.kidx, self.kd2, self.kw), self.A.put(vv_in), self.A.zeros(B, 2, ldy)
+        t = PairTables(ta, tb, ldy, offs, B * 16 * K, vv, vv_in, tabs)
         if fused:
             fsegs = []
             for sg, o_ in zip(segs, offs):
@@ -898,10 +961,7 @@ class DenoiserEngine:
                     assert fs.get(k_) is None or k_ == "addvec"
                 fs.pop("addvec", None)  # (first_mlp's t-embedding rows are added by the consumers, after the ReLU)
                 fsegs.append(fs)
-            self._gemm(feat_in, 4, list(lead_segs) + fsegs,
-                       pair_fused=dict(cob0=seg_offsets(lead_segs)[1] // 32, ld=ldy, K=K, wa=d[0], wb=d[1], ta=ta, tb=tb,
-                                       nbr=self.kidx if fp else None, d2=self.kd2 if fp else None, w=self.kw if fp else None,
-                                       vv_in=d[2] if fp else None, vv=vv))
+            self._gemm(feat_in, 4, list(lead_segs) + fsegs, pair_fused=PairFused(seg_offsets(lead_segs)[1] // 32, K, wa_d, wb_d, vv_d, t))
         else:
             # (lead_segs: other per-point GEMM segments over the same table -- the attention queries -- ride on this launch)
             self._gemm(feat_in, 4, list(lead_segs) + ysegs)
@@ -910,14 +970,10 @@ class DenoiserEngine:
             v2 = ldy <= 2048 and (self.knobs.SLIDE_PAIR_NORM_V2 or self.prec != 1)
             assert (fin is None or v2) and (self.prec == 1 or v2)
             self._emit(make_op(OP_PAIR_NORM, i=(B, ldy, K, 2 if v2 else 1, int(self.prec != 1)),
-                               p=(Y.data_ptr(), self.xyz.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), ed.data_ptr(),
-                                  ta.data_ptr(), tb.data_ptr(), self.kidx.data_ptr() if fp else None,
-                                  self.kd2.data_ptr() if fp else None, self.kw.data_ptr() if fp else None,
-                                  d[2].data_ptr() if fp else None, vv.data_ptr() if fp else None,
-                                  _dp(fin))),
+                               p=(Y.data_ptr(), self.xyz.data_ptr(), wa_d.data_ptr(), wb_d.data_ptr(), ed.data_ptr(), ta.data_ptr(),
+                                  tb.data_ptr(), *map(_dp, tabs or (None,) * 3), _dp(vv_d), _dp(vv), _dp(fin))),
                        name="pair_norm2_kernel<%s, %s>" % ("true" if fp else "false", "_Float16" if self.prec == 1 else "float"))
-        return dict(ta=ta, tb=tb, vv=vv, offs=offs, ldy=ldy, rows=B * 16 * K, vv_in=vv_in,
-                    tabs=(self.kidx, self.kd2, self.kw) if fp else None)
+        return t
 
     def _body_shape(self, mpfx, apfx, npx_log2):
         """(rest, nb1, nbm, nbu) if SLIDE_OP_BLOCK_BODY has an instantiation for this block's widths, else None"""
@@ -947,18 +1003,16 @@ class DenoiserEngine:
             return None
         return shape
 
-    def _emit_block_body(self, body, mpfx, npx_log2, K, out, cvec):
+    def _emit_block_body(self, st, mpfx, out, cvec):
         """SLIDE_OP_BLOCK_BODY (csrc/block_body.hip): Mlp tail -> mo, keys -> u, attention tail, one workgroup per sample,
-        mo / u in registers.  body: state left by _attention's score closure (P, joint GroupNorm rows, ...); ctx: pair tables"""
+        mo / u in registers.  st: the block's AttnState after _attn_scores (end == "body": P, joint GroupNorm rows, pair tables)"""
         sd, B = self.sd, self.B
-        ctx = self.pair_ctx
-        apfx = body["apfx"]
-        npx = 1 << npx_log2
+        ctx, apfx, npx_log2 = st.pair, st.apfx, st.npx_log2
+        assert st.end == "body"
+        npx, K = 1 << npx_log2, 1 << (npx_log2 - 4)
         rest = (mpfx + ".rest_mlp.0.weight") in sd
         vec3 = lambda n, lay, conv, gn: epi_vectors(lay, n, sd[conv + ".bias"], (sd[gn + ".weight"], sd[gn + ".bias"]))
-        a = BodyArgs()
-        keep = []
-        slots = []
+        a, keep, slots = BodyArgs(), [], []
         put16 = lambda w: (lambda t: (keep.append(t), t)[1])(self.A.put(chunk_major(w), torch.float16))
         putf = lambda v: (lambda t: (keep.append(t), t)[1])(self.A.put(np.ascontiguousarray(v, np.float32)))
 
@@ -1003,10 +1057,9 @@ class DenoiserEngine:
             fl += w_sec.size
         a.n_mo, a.gsm, a.invm = n_mo, laym.gs, 1.0 / (laym.gs_logical * npx)
         # keys -> u
-        lay_u = body["lay_u"]
+        lay_u, C2p = st.lay, st.C2p
         n_u = ru(lay_u.width)
-        C1, C2p = body["C1"], body["C2p"]
-        w2k = body["w2"][:, C1:]
+        w2k = self._w(apfx + ".weight_conv.2.weight")[:, st.C1:]
         wk = np.zeros((n_u, C2p), np.float32)
         wk[lay_u.index, :w2k.shape[1]] = w2k
         Wu = put16(wk)
@@ -1015,7 +1068,7 @@ class DenoiserEngine:
         a.n_u, a.gsu, a.nnu, a.invu = n_u, lay_u.gs, lay_u.n_norm, 1.0 / (lay_u.gs_logical * npx)
         fl += w2k.size
         # tail
-        cout = body["cout"]
+        cout = st.cout
         vlay = gn_layout(cout)
         w5 = np.zeros((cout, n_u), np.float32)
         w5[:, lay_u.index] = self._w(apfx + ".weight_conv.5.weight")
@@ -1032,24 +1085,20 @@ class DenoiserEngine:
         a.n_out, a.gsv, a.nnv, a.invv = cout, vlay.gs, vlay.n_norm, 1.0 / (vlay.gs_logical * npx)
         fl += self._w(apfx + ".weight_conv.5.weight").size + wv.size
         # tables and vectors
-        ta, tb = ctx["ta"], ctx["tb"]
+        ta, tb, vv = ctx.t.ta, ctx.t.tb, ctx.t.vv
         a.ta, a.tb, a.t_ld = ta.data_ptr(), tb.data_ptr(), ta.shape[1]
-        a.off1, a.k1, a.offr, a.offk, a.kk = ctx["off1"], c1, ctx["offr"], ctx["offk"], C2p
+        a.off1, a.k1, a.offr, a.offk, a.kk = ctx.off1, c1, ctx.offr, ctx.offk, C2p
         if K == 8:
-            a.vv, a.vbs = ctx["vv"].data_ptr(), 2 * ctx["vv"].shape[2]
-            a.rv = ctx["rvv"].data_ptr()
+            a.vv, a.vbs, a.rv = vv.data_ptr(), 2 * vv.shape[2], ctx.rvv.data_ptr()
             a.nbr, a.d2, a.w = self.kidx.data_ptr(), self.kd2.data_ptr(), self.kw.data_ptr()
-            assert ctx["rvv"].shape[1] == n_mo
-        add0 = ctx["add1"]
+            assert ctx.rvv.shape[1] == n_mo
+        add0 = ctx.add1
         if add0 is not None:
-            a.add0 = add0.vec.data_ptr() + 4 * add0.off
+            a.add0, a.add0_idx = add0.vec.data_ptr() + 4 * add0.off, _dp(add0.idx)
             a.add0_bs, a.add0_stride = add0.bs, add0.idx_stride
-            a.add0_idx = _dp(add0.idx)
-        a.sc = body["scale"].data_ptr() + 4 * body["C1p"]
-        a.sh = body["shift"].data_ptr() + 4 * body["C1p"]
-        a.aff_bs = body["ldT"]
-        a.P, a.p_ld = body["P"].data_ptr(), body["P"].shape[1]
-        assert body["P"].shape[1] >= n_u and out.dtype == torch.float16 and not self._is_cm(out)
+        a.sc, a.sh, a.aff_bs = st.scale.data_ptr() + 4 * st.C1p, st.shift.data_ptr() + 4 * st.C1p, st.ldT
+        a.P, a.p_ld = st.P.data_ptr(), st.P.shape[1]
+        assert st.P.shape[1] >= n_u and out.dtype == torch.float16 and not self._is_cm(out)
         a.out, a.out_ld = out.data_ptr(), out.shape[1]
         a.B = B
         sl = (BodySlot * len(slots))()
@@ -1078,38 +1127,33 @@ class DenoiserEngine:
         vec[3, :gam.shape[0]] = sd[apfx + ".feat_out_conv.1.group_norm.bias"]
         return vec
 
-    def _attention(self, apfx, npx_log2, K, g, q_in, mo, mlp_first, mlp_res, out, out_ld_buf, gather=None, qctx=None,
-                   extra_q=(), pair=None, body=None):
-        """AttentionModule (attention.py:35-96).  g: grouped input [B*npx][ldg]; q_in: query features [B*16][ld];
-        mo: the Mlp output buffer (values input), produced by the caller AFTER the shared first GEMM.
-
+    def _attn_open(self, apfx, npx_log2, q_in, mo, mlp_first, mlp_res, grouped=None, pair=None, qctx=None, extra_q=(), body=False):
+        """AttentionModule (attention.py:35-96), first of three phases: the query GEMM, the shared first layer [first_mlp | res_connect |
+        grouped_feat_conv] and the two syncs.  q_in: query features [B*16][ld]; grouped = (g, gather) of _grouped_input, or pair =
+        (feature table, its channels, coords) for the pair decomposition; mo: the Mlp output buffer (values input), which the caller
+        produces between _attn_scores and _attn_finish; body: the block ends in SLIDE_OP_BLOCK_BODY (_body_shape).
         total_feat = [feat_conv(query) broadcast over the K neighbours | grouped_feat_conv(g)] is never materialised:
         the query half is kept per point ([B*16][C1]); its GroupNorm statistics are its per-point sums x K; and
         because weight_conv.2 is linear, its query half is evaluated once per POINT (a 16-row GEMM) and enters the
         per-neighbour GEMM as a pre-activation add -- 1/K of the reference's MACs for that half.
-        Returns a closure continuing after the caller has produced `mo`."""
+        Returns the AttnState the other two phases take."""
         sd, B = self.sd, self.B
-        rows = B * 16 * K
-        npx = 1 << npx_log2
-        kshift = {8: 3, 16: 4}[K]
-        C1 = sd[apfx + ".feat_conv.weight"].shape[0]
-        C2 = sd[apfx + ".grouped_feat_conv.weight"].shape[0]
-        inter = sd[apfx + ".weight_conv.2.weight"].shape[0]
-        cout = sd[apfx + ".weight_conv.5.weight"].shape[0]
+        K, rows = 1 << (npx_log2 - 4), B << npx_log2
+        assert (grouped is None) != (pair is None)
+        g, gather = grouped or (None, None)
+        C1, C2, cout = (sd[apfx + k_].shape[0] for k_ in (".feat_conv.weight", ".grouped_feat_conv.weight", ".weight_conv.5.weight"))
         C1p, C2p = ru(C1), ru(C2)
         ldT = C1p + C2p                      # physical channel space of the (virtual) concatenation
         issued = qctx is not None  # the query GEMM rode on an earlier block's launch (same input table)
         if qctx is None:
             qctx = self._attention_query(apfx, K)
-        Tq, ssum, ssq = qctx["Tq"], qctx["ssum"], qctx["ssq"]
+        Tq, ssum, ssq, qsegs = qctx.Tq, qctx.ssum, qctx.ssq, [qctx.qseg] + [e.qseg for e in extra_q]
         Tk = None if pair is not None else self._buf(rows, C2p, cm=True)
         kseg = dict(w=self._w(apfx + ".grouped_feat_conv.weight"), bias=sd[apfx + ".grouped_feat_conv.bias"],
                     mode=EPI_STATS, flags=F_PRE_RELU, out=Tk, stats=Stats(ssum, ssq, C1p, 1.0))
         # GroupNorm over the concatenation [q | k] (weight_conv.1): groups may straddle the two producers
-        Ct = C1 + C2
-        G = min(32, Ct)
-        n_norm = Ct - Ct % G
-        gs = n_norm // G
+        Ct, G = C1 + C2, min(32, C1 + C2)
+        n_norm, gs = Ct - Ct % G, Ct // G
         phys = np.array([c if c < C1 else C1p + (c - C1) for c in range(Ct)], np.int64)
         gid = np.full(ldT, -1, np.int32)
         gam, bet = np.zeros(ldT, np.float32), np.zeros(ldT, np.float32)
@@ -1119,24 +1163,16 @@ class DenoiserEngine:
         gstart = np.array([phys[gq * gs] for gq in range(G)], np.int32)
         gend = np.array([phys[(gq + 1) * gs - 1] + 1 for gq in range(G)], np.int32)
         scale, shift = self.A.zeros(B, ldT), self.A.zeros(B, ldT)
-        fin_d = [self.A.put(a) for a in (gid, gstart, gend, gam, bet)]
-
-        def fin_struct():
-            fin = SlideGnFin()
-            for n_, t_ in zip(("sum", "sq", "gid", "gstart", "gend", "gamma", "beta", "scale", "shift"),
-                              (ssum, ssq, fin_d[0], fin_d[1], fin_d[2], fin_d[3], fin_d[4], scale, shift)):
-                setattr(fin, n_, t_.data_ptr())
-            fin.inv_count, fin.C, fin.bs, fin.G = 1.0 / (gs * npx), ldT, ldT, G
-            return self.A.put(np.frombuffer(bytes(fin), dtype=np.uint8).copy())
-
+        fin = SlideGnFin(*(t_.data_ptr() for t_ in [ssum, ssq] + [self.A.put(a) for a in (gid, gstart, gend, gam, bet)] + [scale, shift]),
+                         inv_count=1.0 / (gs << npx_log2), C=ldT, bs=ldT, G=G)  # (the pointers in the structure's field order)
         # lane 1 (query / score branch) forks here: it only needs the module inputs
         self._sync(0, 1)
         q_rides = pair is not None and not issued and q_in is pair[0] and not self.two_lanes
         if not issued and not q_rides:
             self._lane = 1
-            self._gemm(q_in, 4, [qctx["qseg"]] + [e["qseg"] for e in extra_q])
+            self._gemm(q_in, 4, qsegs)
             self._lane = 0
-        pair_fin = False
+        pair_fin, bp = False, None
         # shared-input GEMM: [first_mlp | res_connect | grouped_feat_conv]
         if pair is not None:
             feat_tab, Cf, coords = pair
@@ -1144,16 +1180,12 @@ class DenoiserEngine:
             # (SLIDE_PAIR_NORM_V2=1, opt-in: one 1024-thread workgroup per sample that also finalises the joint GroupNorm -- 3 %
             #  faster for a single chain, 5 % slower with four chains in flight: sixteen waves must find room on ONE CU)
             pair_fin = ldT <= 2048 and (self.knobs.SLIDE_PAIR_NORM_V2 or self.use_gxs)
-            ctx = self._pair_first(npx_log2, K, feat_tab, Cf, [mlp_first, mlp_res, kseg], coords,
-                                   fin=fin_struct() if pair_fin else None,
-                                   lead_segs=([qctx["qseg"]] + [e["qseg"] for e in extra_q]) if q_rides else ())
-            off1, offr, offk = ctx["offs"]
-            ctx.update(off1=off1, offr=offr, offk=offk, lay1=mlp_first["layout"], add1=_rec(AddVec, mlp_first.get("addvec")))
-            rres = ru(mlp_res["w"].shape[0])
-            ctx["rvv"] = None
-            if K == 8:  # coefficient vectors of the two per-slot scalars for the res_connect channels (RAW segment: unscaled)
-                ctx["rvv"] = self.A.put(np.ascontiguousarray(ctx["vv_in"][:, ctx["offr"]:ctx["offr"] + rres]))
-            self.pair_ctx = ctx
+            fin_d = self.A.put(np.frombuffer(bytes(fin), dtype=np.uint8).copy()) if pair_fin else None
+            t = self._pair_first(npx_log2, K, feat_tab, Cf, [mlp_first, mlp_res, kseg], coords, fin=fin_d, lead_segs=qsegs if q_rides else ())
+            offr, rres = t.offs[1], ru(mlp_res["w"].shape[0])
+            # (rvv, K == 8: coefficient vectors of the two per-slot scalars for the res_connect channels -- RAW segment: unscaled)
+            bp = BlockPair(t, *t.offs, mlp_first["layout"], _rec(AddVec, mlp_first.get("addvec")),
+                           self.A.put(np.ascontiguousarray(t.vv_in[:, offr:offr + rres])) if K == 8 else None)
         elif gather is not None and gather.chunks * 32 >= self.knobs.SLIDE_SPLIT_FIRST:
             # (opt-in, SLIDE_SPLIT_FIRST=<min feature channels>: measured neutral to -1.5 % on the feature plan -- the
             # 256-row launch is bound by its epilogue, not by its K loop, and the per-point GEMM is one more launch)
@@ -1168,76 +1200,68 @@ class DenoiserEngine:
             self._gemm(gather.table, 4, [dict(w=sg["w"][:, :Cf], mode=EPI_RAW, out=Y, out_coff=o_,
                                               layout=None if sg.get("layout") is None else sg["layout"].raw())
                                          for sg, o_ in zip(segs, offs)])
-            self._gemm(g, npx_log2, [dict(sg, w=sg["w"][:, Cf:], pre_add=PreAdd(Y, -kshift, o_)) for sg, o_ in zip(segs, offs)],
+            self._gemm(g, npx_log2, [dict(sg, w=sg["w"][:, Cf:], pre_add=PreAdd(Y, 4 - npx_log2, o_)) for sg, o_ in zip(segs, offs)],
                        pre_gather=gather.nbr)
         else:
             self._gemm(g, npx_log2, [mlp_first, mlp_res, kseg], gather=gather)
         self._sync(0, 1)  # the key statistics are ready
+        # how the block ends.  "fused": scores GEMM + values GEMM + softmax-weighted sum in one launch -- csrc/attn_tail.hip, or (round 5)
+        # the same tail in the split arithmetic on float rows (csrc/attn_tail_split.hip attn_tail_split_kernel; SLIDE_TAIL_SPLIT=0:
+        # scores GEMM + values GEMM + combine launch), whose single-accumulator split needs |w| < 32
+        fused = gn_layout(cout).unpermuted and (
+            (self.prec == 1 and self.use_glds and self.knobs.SLIDE_ATTN_TAIL) or
+            (self.use_gxs and self.knobs.SLIDE_TAIL_SPLIT
+             and self._split1_ok(self._w(apfx + ".weight_conv.5.weight"), self._w(apfx + ".feat_out_conv.0.weight"))))
+        return AttnState(apfx, npx_log2, C1, C1p, C2p, ldT, cout, Tq, Tk, scale, shift, fin, pair_fin, bp, mo,
+                         "body" if body else "fused" if fused else "combine")
 
-        def finish_scores():
-            # lane 1.  Joint GroupNorm of [q | k]: finalised by the pair-table pass, inside the per-point query GEMM below
-            # (its small-launch kernel), or by its own launch
-            self._lane = 1
-            d = fin_d
-            # (only the small-launch kernel finalises: same grid bound as run_gemm's dispatch)
-            n_cob_p = ru(gn_layout(inter).width) // 32
-            fuse_fin = (self.prec == 1 and self.use_glds and self.knobs.SLIDE_FUSE_FIN and
-                        ((B * 16 + 63) // 64) * ((n_cob_p + 1) // 2) <= 1024)
-            gn_fin = None
-            if pair_fin:
-                pass
-            elif fuse_fin:  # finalised inside the per-point query GEMM below (its small-launch kernel), one launch less
-                gn_fin = fin_struct()
-            else:
-                self._emit(make_op(OP_FINALIZE_GN, i=(B, ldT, ldT), f=(1.0 / (gs * npx),),
-                                        p=(ssum.data_ptr(), ssq.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(),
-                                           d[3].data_ptr(), d[4].data_ptr(), scale.data_ptr(), shift.data_ptr())))
-            lay = gn_layout(inter)
-            w2 = self._w(apfx + ".weight_conv.2.weight")
-            # query half, once per point: P = W2[:, :C1] . GN(relu(q))      (no bias, raw)
-            P = self.A.zeros(B * 16, ru(lay.width), dtype=self.adt)
-            self._gemm(Tq, 4, [dict(w=w2[:, :C1], mode=EPI_RAW, layout=lay.raw(), out=P)],
-                       in_affine=InAffine(scale, shift, 0, ldT), gn_fin=gn_fin)
-            if body is not None:  # the block body kernel (SLIDE_OP_BLOCK_BODY) takes it from here
-                self._lane = 0
-                body.update(P=P, lay_u=lay, scale=scale, shift=shift, C1=C1, C1p=C1p, C2p=C2p, ldT=ldT, w2=w2, apfx=apfx,
-                            cout=cout, inter=inter)
-                return ("body",)
+    def _attn_scores(self, st):
+        """second phase, the score lane (lane 1): the joint GroupNorm of [q | k] -- finalised by the pair-table pass, inside the
+        per-point query GEMM (its small-launch kernel) or by its own launch --, P, keys -> u, and the scores GEMM unless the tail
+        computes them.  Returns the state with P, u, lay (and S) filled in"""
+        sd, B, apfx, npx_log2, fin, rows = self.sd, self.B, st.apfx, st.npx_log2, st.fin, self.B << st.npx_log2
+        self._lane = 1
+        lay = gn_layout(sd[apfx + ".weight_conv.2.weight"].shape[0])
+        # (only the small-launch kernel finalises: same grid bound as run_gemm's dispatch)
+        fuse_fin = (self.prec == 1 and self.use_glds and self.knobs.SLIDE_FUSE_FIN and
+                    ((B * 16 + 63) // 64) * ((ru(lay.width) // 32 + 1) // 2) <= 1024)
+        gn_fin = None
+        if fuse_fin and not st.pair_fin:  # finalised inside the per-point query GEMM below (its small-launch kernel), one launch less
+            gn_fin = self.A.put(np.frombuffer(bytes(fin), dtype=np.uint8).copy())
+        elif not st.pair_fin:
+            self._emit(make_op(OP_FINALIZE_GN, i=(B, st.ldT, st.ldT), f=(fin.inv_count,),
+                               p=(fin.sum, fin.sq, fin.gid, fin.gstart, fin.gend, fin.gamma, fin.beta, fin.scale, fin.shift)))
+        w2 = self._w(apfx + ".weight_conv.2.weight")
+        aff = lambda off: InAffine(st.scale, st.shift, off, st.ldT)
+        # query half, once per point: P = W2[:, :C1] . GN(relu(q))      (no bias, raw)
+        P = self.A.zeros(B * 16, ru(lay.width), dtype=self.adt)
+        self._gemm(st.Tq, 4, [dict(w=w2[:, :st.C1], mode=EPI_RAW, layout=lay.raw(), out=P)], in_affine=aff(0), gn_fin=gn_fin)
+        u = S = None
+        if st.end != "body":  # (the block body kernel, SLIDE_OP_BLOCK_BODY, takes it from P)
             # neighbour half: u = GN4(relu(W2[:, C1:] . GN(relu(k)) + bias + P[point]))
-            u = self._buf(rows, ru(lay.width), cm=True, fm=self._is_fm(mo))
-            useg = dict(w=w2[:, C1:], bias=sd[apfx + ".weight_conv.2.bias"], mode=EPI_NORM,
-                        flags=F_PRE_RELU, layout=lay, out=u, pre_add=PreAdd(P, kshift),
+            u = self._buf(rows, ru(lay.width), cm=True, fm=self._is_fm(st.mo))
+            useg = dict(w=w2[:, st.C1:], bias=sd[apfx + ".weight_conv.2.bias"], mode=EPI_NORM,
+                        flags=F_PRE_RELU, layout=lay, out=u, pre_add=PreAdd(P, npx_log2 - 4),
                         gn=(sd[apfx + ".weight_conv.4.group_norm.weight"], sd[apfx + ".weight_conv.4.group_norm.bias"]))
-            if pair is not None:  # the keys max(a[q] + b[p], 0) * scale + shift are generated from the pair tables
-                ctx = self.pair_ctx
-                self._gemm(None, npx_log2, [useg], in_affine=InAffine(scale, shift, C1p, ldT),
-                           gx=dict(ta=ctx["ta"], tb=ctx["tb"], coff=ctx["offk"], k_pad=C2p, rows=rows, mode=1, vv=ctx["vv"]),
-                           pair_tabs=ctx["tabs"])
+            if st.pair is not None:  # the keys max(a[q] + b[p], 0) * scale + shift are generated from the pair tables
+                t = st.pair.t
+                self._gemm(None, npx_log2, [useg], in_affine=aff(st.C1p), pair_tabs=t.tabs,
+                           gx=GxArgs(t.ta, t.tb, st.pair.offk, st.C2p, rows, 1, vv=t.vv))
             else:
-                self._gemm(Tk, npx_log2, [useg], in_affine=InAffine(scale, shift, C1p, ldT))
-            vlay = gn_layout(cout)
-            if (self.prec == 1 and self.use_glds and self.knobs.SLIDE_ATTN_TAIL and vlay.unpermuted):
-                self._lane = 0
-                return ("fused", u, lay)  # scores are computed inside the fused attention tail (finish)
-            # round 5: the same tail in the split arithmetic on float rows (csrc/attn_tail_split.hip attn_tail_split_kernel;
-            # SLIDE_TAIL_SPLIT=0: scores GEMM + values GEMM + combine launch).  Its single-accumulator split needs |w| < 32.
-            if (self.use_gxs and self.knobs.SLIDE_TAIL_SPLIT and vlay.unpermuted
-                    and self._split1_ok(self._w(apfx + ".weight_conv.5.weight"), self._w(apfx + ".feat_out_conv.0.weight"))):
-                self._lane = 0
-                return ("fused", u, lay)
-            S = self._buf(rows, cout)
+                self._gemm(st.Tk, npx_log2, [useg], in_affine=aff(st.C1p))
+        if st.end == "combine":
+            S = self._buf(rows, st.cout)
             self._gemm(u, npx_log2, [dict(w=self._w(apfx + ".weight_conv.5.weight"), bias=sd[apfx + ".weight_conv.5.bias"],
                                           mode=EPI_RAW, out=S)], in_cols=lay.index)
-            self._lane = 0
-            return S
+        self._lane = 0
+        return st._replace(P=P, u=u, lay=lay, S=S)
 
-        def finish(S):
-            if isinstance(S, tuple):  # fused tail: scores GEMM + values GEMM + softmax-weighted sum in one launch
-                _, u, lay = S
-                self._attn_tail(apfx, npx_log2, u, lay, mo, out)
-                return
-            self._attn_combine(apfx, npx_log2, S, mo, out)
-        return (finish_scores, finish), cout
+    def _attn_finish(self, st, out):
+        """third phase, after the caller's Mlp tail wrote st.mo: the fused tail, or the values GEMM + join + combine"""
+        if st.end == "fused":
+            return self._attn_tail(st.apfx, st.npx_log2, st.u, st.lay, st.mo, out)
+        assert st.end == "combine"
+        return self._attn_combine(st.apfx, st.npx_log2, st.S, st.mo, out)
 
     def _attn_tail(self, apfx, npx_log2, u, lay, mo, out):
         """the fused end of an AttentionModule as ONE launch (SLIDE_OP_ATTN_TAIL: csrc/attn_tail.hip in fp16, csrc/attn_tail_split.hip in the
@@ -1294,12 +1318,8 @@ class DenoiserEngine:
         """the grouped input of an SA / FP block.  fp16 LDS-DMA path: only the last chunks (left-over feature columns +
         coordinate channels) are assembled; the GEMM gathers the leading 32-column chunks from the neighbours' rows of
         `feat_in` itself (returns (tail buffer, gather tuple)).  Otherwise the whole [rows][Cg] matrix is assembled."""
-        B = self.B
-        rows = B * 16 * K
-        ldg = ru(Cg)
-        nsplit = 0
-        if self.prec == 1 and self.use_glds and self.knobs.SLIDE_GATHER:
-            nsplit = (C // 8) * 8 // 32
+        B, rows, ldg = self.B, self.B * 16 * K, ru(Cg)
+        nsplit = (C // 8) * 8 // 32 if self.prec == 1 and self.use_glds and self.knobs.SLIDE_GATHER else 0
         c_begin = nsplit * 32
         g = self.A.zeros(rows, ldg - c_begin, dtype=self.adt)
         ptrs = (self.xyz.data_ptr(), feat_in.data_ptr(), self.kidx.data_ptr())
@@ -1308,71 +1328,55 @@ class DenoiserEngine:
         # only coordinate channels left: loop-invariant when the coordinates are a fixed condition
         self._emit(make_op(kind, i=(B, C, feat_in.shape[1], ldg, K, self.prec, c_begin, ldg - c_begin), p=ptrs + (g.data_ptr(),)),
                    role="xyz_copy" if nsplit and c_begin == C else None)
-        return g, (Gather(feat_in, self.kidx, K, nsplit) if nsplit else None), rows
+        return g, (Gather(feat_in, self.kidx, K, nsplit) if nsplit else None)
 
     def _sa_module(self, i, feat_in, C, extra_q=()):
         sd, B = self.sd, self.B
         pfx = "SA_modules.%d" % i
         mp, ap = pfx + ".mlps.0", pfx + ".attention_modules.0"
-        K = 16
-        rows = B * 16 * K
-        Cg = C + 9
+        K, rows, Cg = 16, B * 256, C + 9
+        c1, c_last = sd[mp + ".first_mlp.0.weight"].shape[0], sd[mp + ".res_connect.weight"].shape[0]
         assert sd[mp + ".first_mlp.0.weight"].shape[1] == Cg
-        c1 = sd[mp + ".first_mlp.0.weight"].shape[0]
-        c_last = sd[mp + ".res_connect.weight"].shape[0]
         mo = self._buf(rows, c_last, cm=True, fm=self._tail_fm(mp, ap, 8, c_last))
         out = self._buf(B * 16, c_last)
+        pair = grouped = h1 = r = None
         if self.use_gx or self.use_gxs:
             # pair decomposition (csrc/gemm_gx.hip): no grouped input, no h1 / r / key buffers; rows in natural neighbour order
-            first, res = self._mlp_segments(mp, self.tvec, self.cvec, None, None)
             pair = (feat_in, C, dict(rel=C, abs=C + 3, ctr=C + 6))
-            body = {} if self._body_shape(mp, ap, 8) is not None else None
-            (scores, finish), cout = self._attention(ap, 8, K, None, feat_in, mo, first, res, out, None, extra_q=extra_q, pair=pair,
-                                                     body=body)
-            S = scores()
-            if body is not None:
-                self._emit_block_body(body, mp, 8, K, out, self.cvec)
-                return out, cout
-            self._mlp_tail(mp, 8, None, self.cvec, None, mo, pair=self.pair_ctx)
-            finish(S)
-            return out, cout
-        g, gather, _ = self._grouped_input(OP_ASSEMBLE_SA, feat_in, C, Cg, K)
-        h1, r = self._buf(rows, c1, cm=True), self._buf(rows, c_last, cm=True)
-        first, res = self._mlp_segments(mp, self.tvec, self.cvec, h1, r)
-        (scores, finish), cout = self._attention(ap, 8, K, g, feat_in, mo, first, res, out, None, gather=gather, extra_q=extra_q)
-        S = scores()                                  # lane 1: finalize, P, weight_conv.2, weight_conv.5
-        self._mlp_tail(mp, 8, h1, self.cvec, r, mo)   # lane 0: second / rest mlp
-        finish(S)                                     # lane 0: values; join; softmax-combine
-        return out, cout
+        else:
+            grouped = self._grouped_input(OP_ASSEMBLE_SA, feat_in, C, Cg, K)
+            h1, r = self._buf(rows, c1, cm=True), self._buf(rows, c_last, cm=True)
+        first, res = self._mlp_segments(mp, self.tvec, h1, r)
+        st = self._attn_open(ap, 8, feat_in, mo, first, res, grouped, pair, extra_q=extra_q, body=self._body_shape(mp, ap, 8) is not None)
+        st = self._attn_scores(st)                                     # lane 1: finalize, P, weight_conv.2, weight_conv.5
+        if st.end == "body":
+            self._emit_block_body(st, mp, out, self.cvec)
+        else:
+            self._mlp_tail(mp, 8, h1, self.cvec, r, mo, pair=st.pair)  # lane 0: second / rest mlp
+            self._attn_finish(st, out)                                 # lane 0: values; join; softmax-combine
+        return out, st.cout
 
     def _fp_module(self, j, U, CU, Kf, C2, out_buf=None, qctx=None):
         """PointnetKnnFPModule.forward (pointnet2_modules.py:771-873).  U: unknown (skip) features, Kf: known features."""
         sd, B = self.sd, self.B
         pfx = "FP_modules.%d" % j
         m1, m2, ap = pfx + ".mlp1", pfx + ".mlp2", pfx + ".attention_module"
-        K = 8
-        rows = B * 16 * K
-        Cg = C2 + 11
+        K, rows, Cg = 8, B * 128, C2 + 11
+        c1, c_last = sd[m1 + ".first_mlp.0.weight"].shape[0], sd[m1 + ".res_connect.weight"].shape[0]
         assert sd[m1 + ".first_mlp.0.weight"].shape[1] == Cg
-        c1 = sd[m1 + ".first_mlp.0.weight"].shape[0]
-        c_last = sd[m1 + ".res_connect.weight"].shape[0]
         mo = self._buf(rows, c_last, cm=True, fm=self._tail_fm(m1, ap, 7, c_last))
-        pair = h1 = r = g = gather = None
+        pair = grouped = h1 = r = None
         if self.use_gx or self.use_gxs:  # pair decomposition: group_knn's channels are [feats | d2 | w | abs | rel | centre]
             pair = (Kf, C2, dict(d2=C2, w=C2 + 1, abs=C2 + 2, rel=C2 + 5, ctr=C2 + 8))
         else:
-            g, gather, _ = self._grouped_input(OP_ASSEMBLE_FP, Kf, C2, Cg, K)
+            grouped = self._grouped_input(OP_ASSEMBLE_FP, Kf, C2, Cg, K)
             h1, r = self._buf(rows, c1, cm=True), self._buf(rows, c_last, cm=True)
-        first, res = self._mlp_segments(m1, self.tvec, self.cvec, h1, r)
+        first, res = self._mlp_segments(m1, self.tvec, h1, r)
         # mlp2 input: [interpolated (c_last) | unknown feats (CU) | xyz (3)]  (pointnet2_modules.py:842-855)
         zin = c_last + CU + 3
         assert sd[m2 + ".first_mlp.0.weight"].shape[1] == zin
         Z = self._buf(B * 16, zin)
-        body = {} if pair is not None and self._body_shape(m1, ap, 7) is not None else None
-        (scores, finish), cout = self._attention(ap, 7, K, g, U, mo, first, res, Z, None, gather=gather, qctx=qctx, pair=pair,
-                                                 body=body)
-        S = scores()
-        pctx = self.pair_ctx if pair is not None else None
+        st = self._attn_scores(self._attn_open(ap, 7, U, mo, first, res, grouped, pair, qctx=qctx, body=self._body_shape(m1, ap, 7) is not None))
         # skip features and coordinates: columns of Z the attention output does not touch -- on the score lane, beside
         # the value branch (joined by finish)
         es = Z.element_size()
@@ -1398,59 +1402,63 @@ class DenoiserEngine:
                                p=(self.xyz.data_ptr(), Z.data_ptr() + es * (c_last + CU))),
                        role="xyz_copy")  # loop-invariant when the coordinates are a fixed condition
         self._lane = 0
-        if body is not None:
-            self._emit_block_body(body, m1, 7, K, Z, self.cvec)
+        if st.end == "body":
+            self._emit_block_body(st, m1, Z, self.cvec)
         else:
-            self._mlp_tail(m1, 7, h1, self.cvec, r, mo, pair=pctx)
-            finish(S)
-        n1 = sd[m2 + ".first_mlp.0.weight"].shape[0]
-        n2 = sd[m2 + ".res_connect.weight"].shape[0]
+            self._mlp_tail(m1, 7, h1, self.cvec, r, mo, pair=st.pair)
+            self._attn_finish(st, Z)
+        n1, n2 = sd[m2 + ".first_mlp.0.weight"].shape[0], sd[m2 + ".res_connect.weight"].shape[0]
         hz, rz = self._buf(B * 16, n1), self._buf(B * 16, n2)
-        f2, r2 = self._mlp_segments(m2, self.tvec, self.cvec, hz, rz)
+        f2, r2 = self._mlp_segments(m2, self.tvec, hz, rz)
         i0 = len(self.plan)
         self._gemm(Z, 4, [f2, r2])
         out = out_buf if out_buf is not None else self._buf(B * 16, n2)
         self._mlp_tail(m2, 4, hz, self.cvec, rz, out)
         if out_buf is not None:  # the last FP block: its second Mlp may join the output head in one launch (_point_chain)
-            self._chain_front = dict(launches=self.plan[i0:], Z=Z, zin=zin, m2=m2, n1=n1, n2=n2)
+            self._chain_front = ChainFront(self.plan[i0:], Z, zin, m2, n1, n2)
         return out, n2
 
-    def _point_chain(self, dec0, head, w0, w1, lay0):
+    def _head_arrays(self, k0):
+        """the output head fc_lyaer packed on the host for the kernels that run it whole: (W0, W1, b1, v0, n1c) (k0: padded input
+        columns), or None when its shapes are outside what they cover.  Every user uploads its own device copies"""
+        sd, w0, w1 = self.sd, self._w("fc_lyaer.0.weight"), self._w("fc_lyaer.3.weight")
+        lay0, n1c = gn_layout(w0.shape[0]), ru(self.out_dim) // 32
+        if not (self.prec == 1 and w0.shape[0] == 128 and lay0.identity and lay0.gs == 4 and k0 <= 160 and w1.shape[1] == 128
+                and self.out_dim <= 64 and sd["fc_lyaer.1.weight"].shape[0] == 128):
+            return None
+        W0 = np.zeros((128, k0), np.float32); W0[:, :w0.shape[1]] = w0
+        W1 = np.zeros((n1c * 32, 128), np.float32); W1[:w1.shape[0]] = w1
+        b1 = np.zeros(n1c * 32, np.float32); b1[:w1.shape[0]] = sd["fc_lyaer.3.bias"]
+        return W0, W1, b1, epi_vectors(lay0, 128, sd["fc_lyaer.0.bias"], (sd["fc_lyaer.1.weight"], sd["fc_lyaer.1.bias"])), n1c
+
+    def _point_chain(self, dec0, head):
         """round 5: the last FP block's second Mlp + the output head as ONE launch (SLIDE_OP_POINT_CHAIN, csrc/point_chain.hip) -- what
         the kernel needs, or None when the shapes are outside what it covers (fp16 plans; every width 128 with identity GroupNorm layout;
         per-timestep t-embedding table).  The samplers swap it in for the four per-point GEMM launches (diffusion.py); the plan itself
         keeps them (forward() of the engine, parity tests of the layers)."""
         sd, fr = self.sd, getattr(self, "_chain_front", None)
-        if fr is None or self.prec != 1 or not self.knobs.SLIDE_POINT_CHAIN:
+        hd = self._head_arrays(dec0.shape[1])  # (arrays of its own: on the CPU device an upload is the array itself)
+        if fr is None or hd is None or not self.knobs.SLIDE_POINT_CHAIN:
             return None
-        m2 = fr["m2"]
-        ident = lambda c: gn_layout(c).identity and gn_layout(c).gs == 4
+        m2, lay = fr.m2, gn_layout(128)
         c2 = sd[m2 + ".second_mlp.0.weight"].shape[0]
         has_t, has_c = (m2 + ".fc.weight") in sd, (m2 + ".fc_condition.weight") in sd
-        if not (fr["n1"] == 128 and fr["n2"] == 128 and c2 == 128 and (m2 + ".rest_mlp.0.weight") not in sd and ident(128)
-                and len(fr["launches"]) == 2 and self.plan[-4:] == fr["launches"] + head and fr["Z"].shape[1] <= 192 and w0.shape[0] == 128
-                and lay0.identity and lay0.gs == 4 and 128 < dec0.shape[1] <= 160
-                and w1.shape[1] == 128 and self.out_dim <= 64 and sd["fc_lyaer.1.weight"].shape[0] == 128):
+        if not (fr.n1 == 128 and fr.n2 == 128 and c2 == 128 and (m2 + ".rest_mlp.0.weight") not in sd and lay.identity and lay.gs == 4
+                and len(fr.launches) == 2 and self.plan[-4:] == fr.launches + head and fr.Z.shape[1] <= 192 and 128 < dec0.shape[1]):
             return None
-        A = self.A
-        kz, zin = fr["Z"].shape[1], fr["zin"]
+        A, kz, zin = self.A, fr.Z.shape[1], fr.zin
         Wz = np.zeros((256, kz), np.float32)
         Wz[:128, :zin] = self._w(m2 + ".first_mlp.0.weight")
         Wz[128:, :zin] = self._w(m2 + ".res_connect.weight")
         vz = np.stack([sd[m2 + ".first_mlp.0.bias"], sd[m2 + ".first_mlp.1.group_norm.weight"], sd[m2 + ".first_mlp.1.group_norm.bias"],
                        sd[m2 + ".res_connect.bias"]]).astype(np.float32)
-        v2 = epi_vectors(lay0, 128, sd[m2 + ".second_mlp.0.bias"], (sd[m2 + ".second_mlp.1.group_norm.weight"],
-                                                                    sd[m2 + ".second_mlp.1.group_norm.bias"]))
-        n1c = ru(self.out_dim) // 32
-        W0 = np.zeros((128, dec0.shape[1]), np.float32); W0[:, :w0.shape[1]] = w0
-        W1 = np.zeros((n1c * 32, 128), np.float32); W1[:w1.shape[0]] = w1
-        b1 = np.zeros(n1c * 32, np.float32); b1[:w1.shape[0]] = sd["fc_lyaer.3.bias"]
-        v0 = epi_vectors(lay0, 128, sd["fc_lyaer.0.bias"], (sd["fc_lyaer.1.weight"], sd["fc_lyaer.1.bias"]))
+        v2 = epi_vectors(lay, 128, sd[m2 + ".second_mlp.0.bias"], (sd[m2 + ".second_mlp.1.group_norm.weight"],
+                                                                   sd[m2 + ".second_mlp.1.group_norm.bias"]))
+        (W0, W1, b1, v0, n1c), W2 = hd, self._w(m2 + ".second_mlp.0.weight")
         off = lambda lst, pfx: sum(w for _, w in lst[:[p_ for p_, _ in lst].index(pfx)])
-        W2 = self._w(m2 + ".second_mlp.0.weight")
         for role, e in zip(("pc0", "pc1", "pc2", "pc3"), self.plan[-4:]):
             e.roles.add(role)
-        d = dict(Z=fr["Z"], kz=kz, X=dec0, k0=dec0.shape[1], n1c=n1c,
+        d = dict(Z=fr.Z, kz=kz, X=dec0, k0=dec0.shape[1], n1c=n1c,
                  Wz=A.put(Wz, torch.float16), W2=A.put(W2, torch.float16),
                  W0=A.put(W0, torch.float16), W1=A.put(W1, torch.float16), vz=A.put(vz), v2=A.put(v2), v0=A.put(v0), b1=A.put(b1),
                  t_off=off(self._tvec, m2 + ".fc") if has_t else None,
@@ -1568,20 +1576,12 @@ class DenoiserEngine:
         self.eps_pad = self._buf(B * 16, self.out_dim, dtype=torch.float32)
         head[1] = self._gemm(hh, 4, [dict(w=self._w("fc_lyaer.3.weight"), bias=sd["fc_lyaer.3.bias"], mode=EPI_RAW, out=self.eps_pad)])
         # what SLIDE_OP_HEAD_UPDATE needs (the samplers replace the two head GEMMs + their update launch by it, diffusion.py)
-        self.head = None
-        w0, w1 = self._w("fc_lyaer.0.weight"), self._w("fc_lyaer.3.weight")
-        lay0 = gn_layout(w0.shape[0])
-        if (self.prec == 1 and w0.shape[0] == 128 and lay0.identity and lay0.gs == 4
-                and dec0.shape[1] <= 160 and w1.shape[1] == 128 and self.out_dim <= 64 and sd["fc_lyaer.1.weight"].shape[0] == 128):
-            W0 = np.zeros((128, dec0.shape[1]), np.float32); W0[:, :w0.shape[1]] = w0
-            n1c = ru(self.out_dim) // 32
-            W1 = np.zeros((n1c * 32, 128), np.float32); W1[:w1.shape[0]] = w1
-            b1 = np.zeros(n1c * 32, np.float32); b1[:w1.shape[0]] = sd["fc_lyaer.3.bias"]
-            v0 = epi_vectors(lay0, 128, sd["fc_lyaer.0.bias"], (sd["fc_lyaer.1.weight"], sd["fc_lyaer.1.bias"]))
+        self.head, hd = None, self._head_arrays(dec0.shape[1])
+        if hd is not None:
+            W0, W1, b1, v0, n1c = hd
             head[0].roles.add("head0"); head[1].roles.add("head1")
-            self.head = dict(X=dec0, k0=dec0.shape[1], n1c=n1c,
-                             W0=self.A.put(W0, torch.float16), W1=self.A.put(W1, torch.float16), v0=self.A.put(v0), b1=self.A.put(b1))
-        self.point_chain = self._point_chain(dec0, head, w0, w1, lay0)
+            self.head = dict(X=dec0, k0=dec0.shape[1], n1c=n1c, W0=A.put(W0, torch.float16), W1=A.put(W1, torch.float16), v0=A.put(v0), b1=A.put(b1))
+        self.point_chain = self._point_chain(dec0, head)
         self.eps = A.zeros(B, 16, self.out_dim)
         self._emit(make_op(OP_COPY_COLS, i=(B * 16, self.out_dim, self.eps_pad.shape[1], self.out_dim, 0, 0),
                            p=(self.eps_pad.data_ptr(), self.eps.data_ptr())), role="eps_copy")  # samplers read eps_pad and drop this op

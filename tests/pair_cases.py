@@ -2,8 +2,8 @@
 tests/test_hip_pair_arith.py (every case on the GPU against the reference; on the CPU every bound against the mutants).
 
 A case is ONE launch (two for the composition cases) emitted by the engine's own emitters, so the host-side packing is under test too:
-  op "gx"   SLIDE_OP_GEMM_GX, fp16 tables (csrc/gemm_gx.hip, gemm_gx_body)         DenoiserEngine._gemm(gx=...)
-  op "gxs"  SLIDE_OP_GEMM_GX, float tables, split arithmetic (csrc/gemm_gxs.hip)   DenoiserEngine._gemm(gx=..., chain=...)
+  op "gx"   SLIDE_OP_GEMM_GX, fp16 tables (csrc/gemm_gx.hip, gemm_gx_body)         DenoiserEngine._gemm(gx=GxArgs)
+  op "gxs"  SLIDE_OP_GEMM_GX, float tables, split arithmetic (csrc/gemm_gxs.hip)   DenoiserEngine._gemm(gx=GxArgs, chain=_chained_layer)
   op "sa"   SLIDE_OP_SA_CHAIN (csrc/sa_chain.hip, sa_chain_body)                   DenoiserEngine._sa_chain
   op "pf"   SLIDE_OP_PAIR_FIRST (csrc/gemm_small.h, small_body<., ., PAIR>)        DenoiserEngine._pair_first (fp16 plan)
   op "pn"   SLIDE_OP_PAIR_NORM version 2, float tables (csrc/pair_norm.hip)        DenoiserEngine._pair_first (split plan)

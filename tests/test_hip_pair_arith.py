@@ -2,7 +2,7 @@
 SLIDE_OP_PAIR_FIRST, SLIDE_OP_PAIR_NORM version 2 with float tables, SLIDE_OP_GEMM_GX in fp16 and in split arithmetic, SLIDE_OP_SA_CHAIN,
 and PAIR_FIRST -> GEMM_GX against the K-expanded float64 evaluation of the layers they decompose (tests/pair_cases.py: the case matrix
 with its branch -> case table, the references, the derivations and the mutants the bounds must see).  Every launch is emitted by the
-engine's own emitters (_pair_first, _gemm(gx=...), _sa_chain) on a bare plan builder, so the host-side packing -- chunk-major weights,
+engine's own emitters (_pair_first, _gemm(gx=GxArgs), _chained_layer, _sa_chain) on a bare plan builder, so the host-side packing -- chunk-major weights,
 packed epilogue vectors, column offsets, wa = W_rel + W_abs, wb = W_ctr - W_rel -- is under test as well.  Product library only."""
 import ctypes
 
@@ -202,8 +202,8 @@ def _launch_gx(c, d, device):
     pair_tabs = None
     if npxl == 7:
         pair_tabs = (m.A.put(d["nbr"].reshape(-1, 16)), m.A.put(d["d2"]), m.A.put(d["w"]))
-    gx = dict(ta=ta, tb=tb, coff=c["coff"], k_pad=k_pad, rows=rows, mode=c["gxmode"], add=_add_tuple(m, c, d, k_pad),
-              vv=None if npxl == 8 else m.A.put(_window(np.stack([d["vd"], d["vw"]], 1), c, 3e4, 0.25)))
+    gx = E.GxArgs(ta, tb, c["coff"], k_pad, rows, c["gxmode"], _add_tuple(m, c, d, k_pad),
+                  None if npxl == 8 else m.A.put(_window(np.stack([d["vd"], d["vw"]], 1), c, 3e4, 0.25)))
     kw = {}
     if c["gxmode"] == 1:
         pad1 = lambda a, v: np.concatenate([a, np.full((B, k_pad - K), v, np.float32)], 1)
@@ -234,7 +234,7 @@ def _launch_gx(c, d, device):
         seg3.update(out=out, res_pair=res_pair(N2, oidx, Np3))
         if c["add1"]:
             seg["addvec"] = (m.A.put(d["add1"]), 0, N, None, 0)
-        layer2 = m._gemm(None, npxl, [seg3], defer=dict(rows=rows, k_pad=ru(N)))
+        layer2 = m._chained_layer(seg3, npxl, rows, ru(N))
         seg["out"] = None
         L = m._gemm(None, npxl, [seg], gx=gx, pair_tabs=pair_tabs, chain=layer2, **kw)
         Np = Np3
@@ -265,12 +265,14 @@ def _launch_sa(c, d, device):
         t = _alt((B * 16, t_ld), 3e4)
         t[:, off1:off1 + k1], t[:, offr:offr + n2] = a1, ar
         tabs.append(m.A.put(t, torch.float16))
-    pair = dict(ta=tabs[0], tb=tabs[1], vv=None, lay1=(np.arange(k1), k1, k1, 1, 1), off1=off1, offr=offr, add1=_add_tuple(m, c, d, k1))
+    add0 = _add_tuple(m, c, d, k1)
+    pair = E.BlockPair(E.PairTables(tabs[0], tabs[1], t_ld, [off1, offr], B * 256, None, None, None), off1, offr, None,
+                       E.GnLayout(np.arange(k1), k1, k1, 1, 1), None if add0 is None else E.AddVec(*add0), None)
     seg = dict(gn=(d["gamma"], d["beta"]))
     if c["add1"]:
         seg["addvec"] = (m.A.put(d["add1"]), 0, n1, None, 0)
     out = m._buf(B * 256, n2, cm=True, fm=c["out"] == "fm")
-    assert m._sa_chain(pfx, 8, pair, None, seg, out, 0)
+    assert m._sa_chain(pfx, 8, pair, seg, out, 0)
     assert m.plan[-1].name == c["kernel"], (m.plan[-1].name, c["kernel"])
     st = _run(m, 1)
     got = _read_out(m, out, B * 256, n2)
@@ -339,7 +341,7 @@ def _launch_table(c, d, device):
     if c["op"] == "pn":  # the float pass reads y: the case's own, in place of what the per-point GEMM before it would write
         Y = [t for t in m.A.keep if t.data_ptr() == L.op.p[0]][0]
         Yp = np.zeros(tuple(Y.shape), np.float32)
-        for (oidx, _), o_, sg in zip(lays, ctx["offs"], d["segs"]):
+        for (oidx, _), o_, sg in zip(lays, ctx.offs, d["segs"]):
             Yp[:, o_ + oidx] = sg["y"]
         Y.copy_(torch.from_numpy(Yp))
         if c["ld_claim"]:
@@ -358,15 +360,15 @@ def _launch_table(c, d, device):
         if lay2 is not None:
             seg2.update(layout=lay2, gn=(d["gamma2"][:P.gn_params(N2)[1]], d["beta2"][:P.gn_params(N2)[1]]))
         L2 = m._gemm(None, npxl, [seg2], in_cols=lay1[0],
-                     gx=dict(ta=ctx["ta"], tb=ctx["tb"], coff=ctx["offs"][0], k_pad=k_pad, rows=ctx["rows"], mode=0,
-                             add=(m.A.put(addp), 0, k_pad, None, 0), vv=ctx["vv"]), pair_tabs=ctx["tabs"])
+                     gx=E.GxArgs(ctx.ta, ctx.tb, ctx.offs[0], k_pad, ctx.rows, 0, (m.A.put(addp), 0, k_pad, None, 0), ctx.vv),
+                     pair_tabs=ctx.tabs)
         assert L2.name == c["kernel"], (L2.name, c["kernel"])
         n_ops = 2
     st = _run(m, n_ops)
-    got, used = {}, np.zeros(ctx["ldy"], bool)
-    ta, tb = ctx["ta"].float().cpu().numpy(), ctx["tb"].float().cpu().numpy()
-    vv = None if ctx["vv"] is None else ctx["vv"].cpu().numpy()
-    for i, ((oidx, _), o_) in enumerate(zip(lays, ctx["offs"])):
+    got, used = {}, np.zeros(ctx.ldy, bool)
+    ta, tb = ctx.ta.float().cpu().numpy(), ctx.tb.float().cpu().numpy()
+    vv = None if ctx.vv is None else ctx.vv.cpu().numpy()
+    for i, ((oidx, _), o_) in enumerate(zip(lays, ctx.offs)):
         used[o_ + oidx] = True
         got["ta%d" % i], got["tb%d" % i] = ta[:, o_ + oidx], tb[:, o_ + oidx]
         if vv is not None:

@@ -102,6 +102,57 @@ def nets():
     return out
 
 
+def test_a_bare_builder_drives_one_sa_block_through_records(nets, monkeypatch):
+    """the block planner's phases (_attn_open -> _attn_scores -> the Mlp tail -> _attn_finish) on a bare builder, over the state dict of
+    the position net's first SA block (its widths, 32 and 64 channels, are the smallest the emitters take): the launches are the ones
+    the full plan has for that block, the emitters leave no attribute behind on the engine, and what the phases hand over are complete
+    records"""
+    for k in {k for ks in KNOBS for k in ks}:
+        monkeypatch.delenv(k, raising=False)
+    hp, sd = nets["pos"]
+    B, C, mp, ap = 2, 3, "SA_modules.0.mlps.0", "SA_modules.0.attention_modules.0"
+    full = E.DenoiserEngine(hp, sd, B, torch.device("cpu"), prec="fp16")
+    kinds = [e.op.kind for e in full.plan]
+    k0, k1 = kinds.index(E.OP_PREP_POINTS) + 1, kinds.index(E.OP_ATTN_TAIL) + 1
+    assert kinds[k0] == E.OP_PAIR_FIRST and E.OP_PAIR_FIRST not in kinds[k0 + 1:k1]  # (one block)
+
+    m = E.DenoiserEngine.__new__(E.DenoiserEngine)
+    m._plan_state(B, torch.device("cpu"), "fp16")
+    m.use_cm = m.use_gx = True
+    m.use_gxs = False
+    m._cm, m._fm, m._cm_copy, m._tail_of, m._tvec, m._cvec = set(), set(), {}, {}, [], []
+    m.sd = {k: torch.as_tensor(v).detach().numpy().astype("float32") for k, v in sd.items() if k.startswith("SA_modules.0.")}
+    m._n_fc = m._t_bs = m.sd[mp + ".fc.weight"].shape[0]
+    m._c_bs = m.sd[mp + ".fc_condition.weight"].shape[0]
+    m.xyz, m.tvec, m.cvec = m.A.zeros(B * 16, 3), m.A.zeros(B, m._n_fc), m.A.zeros(B, m._c_bs)
+    m._chain_keep, m._dual_keep, m._chain_p_keep, m._pp_keep = [], [], [], []
+    before = set(vars(m))
+
+    c_last = m.sd[mp + ".res_connect.weight"].shape[0]
+    feat, out = m._buf(B * 16, C), m._buf(B * 16, c_last)
+    mo = m._buf(B * 256, c_last, cm=True, fm=m._tail_fm(mp, ap, 8, c_last))
+    first, res = m._mlp_segments(mp, m.tvec, None, None)
+    opened = m._attn_open(ap, 8, feat, mo, first, res, pair=(feat, C, dict(rel=C, abs=C + 3, ctr=C + 6)))
+    st = m._attn_scores(opened)
+    m._mlp_tail(mp, 8, None, m.cvec, None, mo, pair=st.pair)
+    m._attn_finish(st, out)
+    for merge in (m._merge_chains, m._merge_gx_pairs, m._merge_chain_query, m._merge_pp):  # (the passes _build runs, in its order)
+        m.plan = E.rewrite(m.plan, merge())
+
+    assert [e.op.kind for e in m.plan] == kinds[k0:k1]
+    assert [e.name for e in m.plan] == [e.name for e in full.plan[k0:k1]]
+    assert set(vars(m)) == before
+    assert m._tvec == [(mp + ".fc", m._n_fc)] and m._cvec == [(mp + ".fc_condition", m._c_bs)]
+    assert opened.end == st.end == "fused" and opened.P is None and opened.u is None and st.P is not None and st.u is not None and st.S is None
+    assert opened[:-4] == st[:-4]  # (the score phase fills in its own fields and nothing else)
+    for r, T in ((opened, E.AttnState), (st, E.AttnState), (st.pair, E.BlockPair), (st.pair.t, E.PairTables), (st.lay, E.GnLayout),
+                 (st.pair.lay1, E.GnLayout), (st.pair.add1, E.AddVec)):
+        assert type(r) is T and isinstance(r, tuple) and len(r) == len(T._fields) and not hasattr(r, "__dict__"), T
+    assert (st.pair.off1, st.pair.offr, st.pair.offk) == tuple(st.pair.t.offs) and st.pair.rvv is None and st.pair.t.tabs is None
+    t = st.pair.t  # (the pair tables read by name as well as by position, and a dict of the fields makes the record)
+    assert t["ta"] is t.ta is t[0] and t["offs"] is t.offs and E._rec(E.PairTables, t._asdict()) == t
+
+
 @pytest.mark.parametrize("B", [2, 600])
 @pytest.mark.parametrize("prec", ["fp16", "split", "fp32"])
 @pytest.mark.parametrize("net", ["pos", "feat"])
