@@ -21,6 +21,9 @@
  *
  * Part 5 is DPSR, oriented points to the Poisson indicator grid (the reference's pointnet2/dpsr_utils/dpsr.py), forward and backward.
  *
+ * Part 6 is marching cubes, the indicator grid to an indexed triangle mesh (the reference calls skimage.measure.marching_cubes on the
+ * host: pointnet2/dpsr_utils/utils.py mc_from_psr).
+ *
  * Part 3 is the fused latent-DDPM denoiser engine (the reference runs these as ~80 torch module
  * launches per step: pointnet2/models/pointnet2_with_pcld_condition.py:286-489).
  */
@@ -210,6 +213,30 @@ SLIDE_API int slide_dpsr_grid_bwd(int b, int n, int r, const float *pts, const f
                                   const float *coef, const float *gout, int shift, int scale, long long *ws_w, float *ws_ones,
                                   float *ws_dpre, float *ws_spec, float *ws_spec3, float *ws_dras, double *ws_part, double *ws_sums,
                                   float *dv, float *dn, int *flag, slide_stream_t stream);
+
+/* ------------------------------------------------------------------ Part 6: marching cubes, grid -> indexed triangle mesh */
+/* phi (b,r,r,r) f32, flat index (i r + j) r + k, 2 <= r <= 256 (any r, not only the FFT sizes).  A grid point is inside iff
+ * phi < level (a NaN is outside).  One vertex per grid edge whose ends differ in that predicate, at p + t e_axis with
+ * t = (level - a) / (b - a) in fp32 (a at the lower-index end p); its normal is the central-difference gradient of phi (one-sided on
+ * the border) at the edge's two ends, interpolated with t, normalised and NEGATED (0 for a zero gradient); every cell emits the
+ * triangles of its 8-bit case from csrc/marching_cubes_table.h, wound so that (v1 - v0) x (v2 - v0) points toward increasing phi.
+ * The arithmetic, the brick decomposition and the order of the output are written out in csrc/marching_cubes.hip.  No atomics: a
+ * grid's mesh is bit-identical in any batch, at any position and over repeated runs.  Both entry points return -2 for r outside
+ * [2, 256], b < 0, a NULL pointer with b > 0 or more than 2^31 - 1 workgroups (b * slide_mc_bricks(r)), and 0 without a launch for
+ * b = 0.
+ *
+ * The number of bricks (workgroups) per grid of size r; -2 for r outside [2, 256]. */
+SLIDE_API int slide_mc_bricks(int r);
+/* Count: counts_ws (b, slide_mc_bricks(r), 2) int32 receives every brick's first vertex and first triangle WITHIN its grid (the
+ * exclusive prefix of the brick counts, in brick order); totals (b,4) int64 = per grid (V, F, the grid's first row in verts /
+ * normals, its first row in faces) when the b meshes are stored one after the other.  Three launches.  The caller reads totals to
+ * size the outputs. */
+SLIDE_API int slide_mc_count(int b, int r, const float *phi, float level, int *counts_ws, long long *totals, slide_stream_t stream);
+/* Emit, with counts_ws and totals as slide_mc_count left them (same phi, level): verts, normals (sum V, 3) f32, verts in grid-index
+ * units; faces (sum F, 3) int32, vertex indices LOCAL to the grid (0 .. V - 1); ws (b,r,r,r) int32 workspace.  Two launches.  Not
+ * to be called when sum V is 0 (there is nothing to write and the output pointers would be NULL). */
+SLIDE_API int slide_mc_emit(int b, int r, const float *phi, float level, const int *counts_ws, const long long *totals, float *verts,
+                            float *normals, int *faces, int *ws, slide_stream_t stream);
 
 /* ------------------------------------------------------------------ Part 3: denoiser engine */
 /* see slide_engine.h */

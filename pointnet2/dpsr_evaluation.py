@@ -1,6 +1,10 @@
 """Point clouds -> DPSR indicator grids: the coordinate transformations of the reference's pointnet2/dpsr_evaluation.py
-(shapenet_psr_normalize lines 22-32, compute_center_and_max_length 34-43, the tail of network_output_to_dpsr_grid 77-86).  The
-refine-and-upsample network in front of them and the evaluation loop behind them are not part of this build."""
+(shapenet_psr_normalize lines 22-32, compute_center_and_max_length 34-43, the tail of network_output_to_dpsr_grid 77-86), and DPSR
+grids -> meshes on disk (batch_mc_from_psr 291-340).  The refine-and-upsample network in front of them and the evaluation loop behind
+them are not part of this build."""
+import os
+
+import numpy as np
 import torch
 
 
@@ -28,3 +32,25 @@ def points_to_dpsr_grid(points, normals, dpsr, scale=1, explicit_normalize=False
         points = points / scale / 2
     points = torch.clamp(points / 1.2 + 0.5, min=0, max=0.99).contiguous()
     return dpsr(points, normals.contiguous()), points, normals
+
+
+def batch_mc_from_psr(psr_grid, save_dir, save_prefix, batch_info=None, start_idx=0, sample_points_from_mesh=False,
+                      return_original_scale=False, original_center=None, original_max_length=None):
+    """marching cubes of psr_grid (B, res, res, res) and one PLY per shape: <save_prefix>_<start_idx + i:05d>.ply under save_dir (or
+    <batch_info[i]>_<...>.ply).  The vertices are in [0, 1) (divided by res); with return_original_scale the mesh's bounding box is
+    mapped to original_center (B, 1, 3) and original_max_length (B, 1, 1).  Returns the reference's four lists, which only its
+    sample_points_from_mesh fills: that path (pytorch3d's sample_points_from_meshes + FPS) is not part of this build."""
+    from dpsr_utils.io_utils import save_mesh
+    from dpsr_utils.utils import mc_from_psr
+    if sample_points_from_mesh:
+        raise NotImplementedError("batch_mc_from_psr: sampling points from the meshes is not part of this build")
+    vs, fs, ns = mc_from_psr(psr_grid, zero_level=0)  # (one launch sequence for the batch; a grid's mesh does not depend on it)
+    for i, (v, f, n) in enumerate(zip(vs, fs, ns)):
+        if return_original_scale:
+            box = torch.from_numpy(np.ascontiguousarray(v)).to(psr_grid.device)[None]
+            center, max_length = compute_center_and_max_length(box)
+            box = (box - center) / max_length * original_max_length[i:i + 1] + original_center[i:i + 1]
+            v = box[0].cpu().numpy()
+        stem = save_prefix if batch_info is None else batch_info[i]
+        save_mesh(os.path.join(save_dir, "%s_%05d.ply" % (stem, start_idx + i)), v, f, normals=n)
+    return [], [], [], []

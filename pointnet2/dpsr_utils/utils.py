@@ -5,6 +5,11 @@ same names, arguments and return shapes; 3-D cubic grids, CUDA float tensors, fo
   point_rasterize(pts, vals, size) trilinear scatter, (B, nf, r, r, r) float: converted once per cell from the kernel's exact
                                    64-bit fixed-point sums (bit-reproducible, unlike a float scatter_add_)
   grid_interp(grid, pts, batched)  trilinear gather, (B, n, C)
+
+and its mesh helpers (lines 246-287, 498-507) on slide_amd/mesh.py:
+
+  mc_from_psr(psr_grid, ...)       marching cubes of every grid of a batch on the GPU, (verts, faces, normals) lists of length B
+  export_mesh(name, v, f)          a binary PLY of one mesh
 """
 import numpy as np
 import torch
@@ -46,3 +51,30 @@ def grid_interp(grid, pts, batched=True):
     if not batched:
         return _hip.grid_interp(grid.unsqueeze(0), pts.unsqueeze(0)).squeeze(0)
     return _hip.grid_interp(grid, pts)
+
+
+def mc_from_psr(psr_grid, pytorchify=False, real_scale=False, zero_level=0):
+    """psr_grid (B, s, s, s) CUDA float -> three lists of length B: verts (V, 3) divided by s (by s - 1 with real_scale), faces (F, 3)
+    int32, normals (V, 3): numpy arrays, or with pytorchify float tensors on the grid's device with the normals NEGATED (the
+    reference's torch.Tensor(...) conversion: the faces become floats too).  Like the reference, zero_level is honoured for a batch
+    of one only; larger batches are cut at level 0."""
+    from slide_amd import mesh
+    B, s = psr_grid.shape[0], psr_grid.shape[-1]
+    meshes = mesh.marching_cubes(psr_grid.detach(), level=zero_level if B == 1 else 0)
+    unit = (s - 1) if real_scale else s  # vertices to [0, 1] or to [0, 1)
+    verts = [v.cpu().numpy() / unit for v, _, _ in meshes]
+    faces = [f.cpu().numpy() for _, f, _ in meshes]
+    normals = [n.cpu().numpy() for _, _, n in meshes]
+    if pytorchify:
+        def as_float(a):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(psr_grid.device)
+        verts, faces, normals = [as_float(v) for v in verts], [as_float(f) for f in faces], [as_float(-n) for n in normals]
+    return verts, faces, normals
+
+
+def export_mesh(name, v, f):
+    """one mesh as a binary PLY; v (V, 3) / f (F, 3) arrays or tensors, or batched with a leading axis (the first one is written)"""
+    from slide_amd import mesh
+    if len(v.shape) > 2:
+        v, f = v[0], f[0]
+    mesh.save_ply(name, v, f)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Generated point clouds -> Poisson indicator grids, on the HIP DPSR (dpsr_utils/dpsr.py): the step between the generation /
-decode CLIs and a mesh extractor.
+decode CLIs and the meshes (--save_mesh_dir: marching cubes on the GPU, slide_amd/mesh.py).
 
   --points x.npz               npz with `points` (n, N, 3) and `normals` (n, N, 3) -- what autoencoder_decode_keypoint.py writes
                                (reconstructed_pcd.npz) -- or with --split_points_to_normals `points` (n, N, 6): xyz + normals
@@ -9,6 +9,8 @@ decode CLIs and a mesh extractor.
   --grid_res 128 --psr_sigma 2 the DPSR grid and its Gaussian smoothing
   --batch_size B               clouds per DPSR call
   --save out.npz               receives `psr_grid` (n, r, r, r), `points` (n, N, 3) as DPSR saw them (in [0, 0.99]) and `normals`
+  --save_mesh_dir DIR          also one triangle mesh per shape, DIR/<prefix>_<index:05d>.ply (vertices in [0, 1), with normals)
+  --mesh_prefix P              ... the prefix (default mesh)
 """
 import argparse
 import os
@@ -31,10 +33,12 @@ def main():
     ap.add_argument("--psr_sigma", type=float, default=2)
     ap.add_argument("--batch_size", type=int, default=32)
     ap.add_argument("--save", type=str, required=True)
+    ap.add_argument("--save_mesh_dir", type=str, default=None, help="also write one PLY mesh per shape into this directory")
+    ap.add_argument("--mesh_prefix", type=str, default="mesh")
     a = ap.parse_args()
 
     import torch
-    from dpsr_evaluation import points_to_dpsr_grid
+    from dpsr_evaluation import batch_mc_from_psr, points_to_dpsr_grid
     from dpsr_utils.dpsr import DPSR
 
     src = np.load(a.points, allow_pickle=True)
@@ -54,15 +58,21 @@ def main():
     dev = torch.device("cuda:0")
     dpsr = DPSR((a.grid_res,) * 3, sig=a.psr_sigma).to(dev)
     grids, pts = [], []
+    if a.save_mesh_dir:
+        os.makedirs(a.save_mesh_dir, exist_ok=True)
     for s in range(0, points.shape[0], a.batch_size):
         grid, p, _ = points_to_dpsr_grid(torch.from_numpy(np.ascontiguousarray(points[s:s + a.batch_size])).to(dev),
                                          torch.from_numpy(np.ascontiguousarray(normals[s:s + a.batch_size])).to(dev), dpsr,
                                          scale=a.scale, explicit_normalize=a.explicit_normalize)
         grids.append(grid.cpu().numpy())
         pts.append(p.cpu().numpy())
+        if a.save_mesh_dir:
+            batch_mc_from_psr(grid, a.save_mesh_dir, a.mesh_prefix, start_idx=s)
     os.makedirs(os.path.dirname(os.path.abspath(a.save)), exist_ok=True)
     np.savez(a.save, psr_grid=np.concatenate(grids), points=np.concatenate(pts), normals=normals)
     print("psr_grid %s has been saved to %s" % (np.concatenate(grids).shape, a.save))
+    if a.save_mesh_dir:
+        print("%d meshes have been saved to %s" % (points.shape[0], a.save_mesh_dir))
 
 
 if __name__ == "__main__":

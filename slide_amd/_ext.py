@@ -711,3 +711,50 @@ def dpsr_grid_backward(pts, normals, G, phi, coef, g, shift=True, scale=True, ne
               "dpsr_grid_backward")
     _raise_dpsr_flag(flag, "dpsr_grid_backward")
     return dv, dn
+
+
+# ---------------------------------------------------------------------------------------------------------------- marching cubes
+MC_RMAX = 256
+_MC_WORKSPACE_BYTES = 1 << 30  # marching_cubes' default chunk: as many grids as keep the per-point id volume within this
+
+
+def mc_bricks(r):
+    """workgroups per grid of slide_mc_count / slide_mc_emit (slide_mc_bricks)"""
+    n = lib().slide_mc_bricks(int(r))
+    if n < 0:
+        raise ValueError("marching_cubes: the grid resolution must be in [2, %d], got %r" % (MC_RMAX, r))
+    return n
+
+
+def marching_cubes(phi, level=0.0, chunk=None):
+    """slide_mc_count + slide_mc_emit: phi (B,r,r,r) f32, 2 <= r <= 256 -> a list of B tuples (verts (V,3) f32 in grid-index units,
+    faces (F,3) int32 local to the grid, normals (V,3) f32).  Grids run `chunk` at a time (default: the int32 id volume stays within
+    1 GiB); a grid's mesh does not depend on the chunk, the batch or its position.  One host read of the per-grid totals per chunk
+    sizes the outputs."""
+    phi = _chk_f32_cuda(phi, "phi", 4)
+    B, r = phi.size(0), phi.size(1)
+    if phi.size(2) != r or phi.size(3) != r:
+        raise ValueError("marching_cubes: cubic grids (B,r,r,r) only, got %s" % (tuple(phi.shape),))
+    nbricks = mc_bricks(r)
+    if chunk is not None and int(chunk) < 1:
+        raise ValueError("chunk must be positive")
+    cb = max(1, min(B, int(chunk) if chunk is not None else _MC_WORKSPACE_BYTES // (4 * r ** 3)))
+    dev, out = phi.device, []
+    f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
+    if B == 0:
+        return out
+    counts = torch.empty((cb, nbricks, 2), **i32)
+    totals = torch.empty((cb, 4), device=dev, dtype=torch.int64)
+    ws = torch.empty((cb, r, r, r), **i32)
+    for s in range(0, B, cb):
+        e = min(s + cb, B)
+        check(lib().slide_mc_count(e - s, r, ptr(phi[s:e]), float(level), ptr(counts), ptr(totals), stream_of()), "mc_count")
+        tot = totals[:e - s].cpu().tolist()
+        nv, nf = sum(t[0] for t in tot), sum(t[1] for t in tot)
+        verts, normals, faces = torch.empty((nv, 3), **f32), torch.empty((nv, 3), **f32), torch.empty((nf, 3), **i32)
+        if nv:
+            check(lib().slide_mc_emit(e - s, r, ptr(phi[s:e]), float(level), ptr(counts), ptr(totals), ptr(verts), ptr(normals),
+                                      ptr(faces), ptr(ws), stream_of()), "mc_emit")
+        for v, f, v0, f0 in tot:
+            out.append((verts[v0:v0 + v], faces[f0:f0 + f], normals[v0:v0 + v]))
+    return out

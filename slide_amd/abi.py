@@ -184,6 +184,9 @@ PROTOTYPES = {name: _proto(args) for name, args in {
     "slide_dpsr_spectral_adj": "iipppp",
     "slide_dpsr_bwd_points": "iiippppppiipppp",
     "slide_dpsr_grid_bwd": "iiippppppii" + "p" * 12,
+    "slide_mc_bricks": "i",
+    "slide_mc_count": "iipfppp",
+    "slide_mc_emit": "iipfppppppp",
     "slide_hip_device_ok": "",
     "slide_lane_reduce_selftest": "pppip",
     "slide_philox_normal_selftest": "iiiiiipp",
