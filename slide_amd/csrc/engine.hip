@@ -704,6 +704,8 @@ int run_op(const SlideOp &o, hipStream_t s) {
       const int esz = o.i[5] == SLIDE_PREC_F16 ? 2 : 4;
       const int c_begin = o.i[6], ld_out = o.i[6] ? o.i[7] : o.i[3];
       const int nch = o.i[3] / 8, nbulk = (esz * o.i[2] % 16 == 0) ? o.i[1] / 8 : 0, ntail = nch - nbulk;
+      // the element-wise pieces start at column 8 nbulk: with c_begin beyond it they would be stored in front of their row
+      if (c_begin < 0 || c_begin % 8 || c_begin > nbulk * 8) return -3;
       const int nb_eff = nbulk - c_begin / 8 > 0 ? nbulk - c_begin / 8 : 0;
       int nch_log2 = 0;
       while ((1 << nch_log2) < nb_eff) ++nch_log2;

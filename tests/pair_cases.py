@@ -24,10 +24,20 @@ branch of the product build's launchers                | cases
   pair_norm2_kernel<false / true, float, 512>          | pn_k16_32, pn_k16_544_fin, pn_k16_cluster / pn_k8_32, pn_k8_2048_fin;  pn_2080: -3
                                                        | (ld 32, 544 = two passes of 320 threads, 2048 = the limit, 2080 refused)
   PAIR_FIRST -> GEMM_GX                                | comp_k16, comp_k8
+  gemm_gx_dual_kernel<7> (SLIDE_OP_GEMM_GX_DUAL)       | dual_n7 = gx_n7_m1_n64 + gx_n7_m0_n64w in ONE launch through the host-pointer form
+  SLIDE_OP_GEMM_GX_DUAL, LDS does not fit              | dual_n7_two_launches = gx_n7_m1_k1568 (gemm_gx_n64w_kernel<7, 3, 1>) + gx_n7_m0_w128_2st:
+                                                       | the launcher falls back to the two single launches
+  sa_chain_p_kernel<4> (SLIDE_OP_SA_CHAIN_P)           | sa_p_64_128_256 = sa_64_128_256 + the 16-row query GEMM f16_n4_norm_aff of gemm_cases
+                                                       | (its B set to the chain's: the launcher wants rows == 16 B)
 LDS thresholds (launch_gx, csrc/gemm_gx.hip: shm = NST (4096 CBW + 4096 NSAMP) + (40 CBW + 96 CBW) 4 + 2 NSAMP NVEC k_pad + 16, NSAMP = 1 / 2
 samples per tile, NVEC = 1 (mode 0) / 2 (mode 1) + 2 (128-row samples)):  64-channel tiles, three stages: 36864 (49152) + 1104 +
 2 NSAMP NVEC k_pad <= 53 KB for the three-per-CU form -> k_pad <= 4076 (256 rows, mode 1), <= 251 (128 rows, mode 1); 128-channel tiles,
 three stages: 61440 (73728) + 2192 + ... <= 80 KB -> k_pad <= 9144 / 4572 (256 rows, mode 0 / 1), <= 500 / 375 (128 rows): beyond that two.
+
+HOST-POINTER PAIRS (DUAL, CHAIN_P).  p[0] of the op is a HOST pointer to two SlideOps; every output is held to the float64 reference and
+bound its single-launch case already has.  The dual form runs both GEMMs on 64-channel tiles with NST = 2 (128-row samples) / 3 ring
+stages: dual_lds() restates launch_gx_dual's LDS, NST (8192 + 4096 NSAMP) + (2 EPI_DW + 192) 4 + 2 NSAMP NVEC k_pad + 16 <= 53 KB (128-row
+samples) / 80 KB: at 128-row samples mode 1 fits up to k_pad 1274, so k_pad 1568 is the two-launch fallback.
 
 GENERATED X (fp16; gemm_gx_body::compute_step, sa_chain_body::compute1).  r16 = one rounding to fp16:
   y = r16(ta[q] + tb[p]);  128-row samples: y = r16(d2h vdh + y), y = r16(wh vwh + y) (fp16 FMAs), d2h = r16(min(d2, 65504));
@@ -131,6 +141,8 @@ GX = [
     _p("gx_n7_m1_w128", "gx", "fp16", 7, 9, 35, 64, 64, EPI_RAW, "gemm_gx_kernel<7, 3, 1>", "common", gxmode=1, env=N64OFF, out="cm"),
     _p("gx_n7_m0_w128_2st", "gx", "fp16", 7, 1, 543, 544, 32, EPI_STATS, "gemm_gx_kernel<7, 2, 0>", "small", add="plain", pre_relu=True, env=N64OFF),
     _p("gx_n7_m1_w128_2st", "gx", "fp16", 7, 3, 544, 544, 51, EPI_NORM, "gemm_gx_kernel<7, 2, 1>", gxmode=1, post_relu=True, env=N64OFF),
+    # (beyond the dual form's LDS: the mode-1 half of dual_n7_two_launches)
+    _p("gx_n7_m1_k1568", "gx", "fp16", 7, 1, 1568, 1568, 32, EPI_RAW, "gemm_gx_n64w_kernel<7, 3, 1>", gxmode=1),
 ]
 GXS = [
     _p("gxs_n8_m0", "gxs", "split", 8, 3, 35, 64, 111, EPI_NORM, "gemm_gxs_kernel<8, 0>", "bigw", add="idx", post_relu=True, pair=True, coff=8, t_extra=4),
@@ -149,6 +161,19 @@ SA = [
     _p("sa_128_128_512", "sa", "fp16", 8, 9, 128, 128, 128, EPI_NORM, "sa_chain_kernel<4>", add="idx", add1=True, out="cm", chain=dict(N=512)),
 ]
 CASES = GX + GXS + SA
+# the host-pointer pair launches (module docstring)
+DUAL = [dict(name="dual_n7", m1="gx_n7_m1_n64", m0="gx_n7_m0_n64w", fits=True),
+        dict(name="dual_n7_two_launches", m1="gx_n7_m1_k1568", m0="gx_n7_m0_w128_2st", fits=False)]
+CHAIN_P = [dict(name="sa_p_64_128_256", sa="sa_64_128_256", q=dict(G.CASE_BY_NAME["f16_n4_norm_aff"], B=3), kernel="sa_chain_p_kernel<4>")]
+
+
+def dual_lds(c, epi_dw):
+    """launch_gx_dual's dynamic LDS of one half (csrc/gemm_gx.hip) and its limit"""
+    nsamp = 256 >> c["npxl"]
+    nst = 2 if c["npxl"] == 7 else 3
+    nvec = (2 if c["gxmode"] else 1) + (2 if c["npxl"] == 7 else 0)
+    return nst * (8192 + 4 * 64 * 16 * nsamp) + (2 * epi_dw + (2 * epi_dw) % 4 + 2 * 96) * 4 + nsamp * nvec * c["k_pad"] * 2 + 16, \
+        (53 if c["npxl"] == 7 else 80) * 1024
 CASE_BY_NAME = {c["name"]: c for c in CASES}
 KERNELS = (["gemm_gx_n64_kernel<%d, 3, 1>" % n for n in (7, 8)] + ["gemm_gx_n64w_kernel<%d, 3, %d>" % (n, m) for n in (7, 8) for m in (0, 1)] +
            ["gemm_gx_kernel<%d, %d, %d>" % (n, s, m) for n in (7, 8) for s in (3, 2) for m in (0, 1)] +

@@ -172,8 +172,8 @@ def _add_tuple(m, c, d, width):
     return None
 
 
-def _launch_gx(c, d, device):
-    """emits and runs a generated-X GEMM case; returns (status, got [rows][N], padded output columns, stats or None)"""
+def _emit_gx(c, d, device):
+    """emits a generated-X GEMM case on a plan builder of its own; returns what reading its outputs needs"""
     import torch
     from slide_amd import engine as E
     prec, B, K, k_pad, N, npxl = c["prec"], c["B"], c["K"], c["k_pad"], c["N"], c["npxl"]
@@ -239,14 +239,26 @@ def _launch_gx(c, d, device):
         L = m._gemm(None, npxl, [seg], gx=gx, pair_tabs=pair_tabs, chain=layer2, **kw)
         Np = Np3
     assert L.name == c["kernel"], (L.name, c["kernel"])
-    st = _run(m, 1)
-    got = _read_out(m, out, rows, Np)
-    stats = None if ssum is None else (ssum.cpu().numpy()[:, oidx], ssq.cpu().numpy()[:, oidx])
-    return st, got[:, oidx], np.delete(got, oidx, axis=1), stats
+    return dict(m=m, out=out, rows=rows, Np=Np, oidx=oidx, ssum=ssum, ssq=ssq)
 
 
-def _launch_sa(c, d, device):
-    """emits and runs an SA-chain case through _sa_chain; returns (status, got [rows][n2], no padded columns, None)"""
+def _read_gx(e):
+    """(got [rows][N], padded output columns, stats or None) of an emitted generated-X case after its launch"""
+    got = _read_out(e["m"], e["out"], e["rows"], e["Np"])
+    oidx = e["oidx"]
+    stats = None if e["ssum"] is None else (e["ssum"].cpu().numpy()[:, oidx], e["ssq"].cpu().numpy()[:, oidx])
+    return got[:, oidx], np.delete(got, oidx, axis=1), stats
+
+
+def _launch_gx(c, d, device):
+    """emits and runs a generated-X GEMM case; returns (status, got [rows][N], padded output columns, stats or None)"""
+    e = _emit_gx(c, d, device)
+    st = _run(e["m"], 1)
+    return (st,) + _read_gx(e)
+
+
+def _emit_sa(c, d, device):
+    """emits an SA-chain case through _sa_chain; returns (plan builder, output buffer)"""
     import torch
     from slide_amd import engine as E
     B, k1, n1, n2 = c["B"], c["K"], c["N"], c["chain"]["N"]
@@ -274,9 +286,14 @@ def _launch_sa(c, d, device):
     out = m._buf(B * 256, n2, cm=True, fm=c["out"] == "fm")
     assert m._sa_chain(pfx, 8, pair, seg, out, 0)
     assert m.plan[-1].name == c["kernel"], (m.plan[-1].name, c["kernel"])
+    return m, out
+
+
+def _launch_sa(c, d, device):
+    """emits and runs an SA-chain case; returns (status, got [rows][n2], no padded columns, None)"""
+    m, out = _emit_sa(c, d, device)
     st = _run(m, 1)
-    got = _read_out(m, out, B * 256, n2)
-    return st, got, np.zeros((1, 0)), None
+    return st, _read_out(m, out, c["B"] * 256, c["chain"]["N"]), np.zeros((1, 0)), None
 
 
 def _launch_table(c, d, device):
@@ -466,3 +483,108 @@ def test_pair_op_matches_float64(gpu_device, monkeypatch, name):
             rs = float((np.abs(stats[k] - ref["stats"][k]) / ref["stats_b"][k]).max())
             print("%s: statistics %s worst err/tol %.3g" % (name, ("sum", "sq")[k], rs))
             assert rs <= 1, (name, k, rs)
+
+
+# ------------------------------------------------------------------------------------------------------------ host-pointer pairs
+def _run_pair(kind, rows_or_b, op_a, op_b):
+    """one launch of a host-pointer pair op (SLIDE_OP_GEMM_GX_DUAL / SLIDE_OP_SA_CHAIN_P): p[0] -> two SlideOps in host memory"""
+    import torch
+    from slide_amd import abi
+    from slide_amd._lib import lib
+    pair = (abi.SlideOp * 2)(abi.SlideOp.from_buffer_copy(bytes(op_a)), abi.SlideOp.from_buffer_copy(bytes(op_b)))
+    ops = (abi.SlideOp * 1)(abi.make_op(kind, i=(rows_or_b,), p=(ctypes.addressof(pair),)))
+    st = lib().slide_run_ops(ops, 1, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    return st
+
+
+def _hold(name, kernel, got, ref, pad, stats=None):
+    assert np.isfinite(got).all()
+    ratio = np.abs(got - ref["y"]) / ref["b"]
+    i = np.unravel_index(np.argmax(ratio), ratio.shape)
+    print("%s [%s]: worst err/tol %.3g (|ref| %.3g at %s)" % (name, kernel, ratio[i], abs(ref["y"][i]), i))
+    assert ratio.max() <= 1, (name, float(ratio.max()), i)
+    assert (pad == 0).all(), "padded output columns must be zero"
+    if stats is not None:
+        for k in range(2):
+            rs = float((np.abs(stats[k] - ref["stats"][k]) / ref["stats_b"][k]).max())
+            print("%s: statistics %s worst err/tol %.3g" % (name, ("sum", "sq")[k], rs))
+            assert rs <= 1, (name, k, rs)
+
+
+def test_dual_rows_fit_and_do_not_fit():
+    """the LDS of the dual form (pair_cases.dual_lds): the first row runs as ONE launch, the second takes the launcher's fallback"""
+    from slide_amd import abi
+    epi_dw = ctypes.sizeof(abi.SlideEpi) // 4
+    for row in P.DUAL:
+        c1, c0 = CASE_BY_NAME[row["m1"]], CASE_BY_NAME[row["m0"]]
+        assert c1["gxmode"] == 1 and c0["gxmode"] == 0 and c1["B"] == c0["B"] and c1["npxl"] == c0["npxl"] and c1["prec"] == c0["prec"] == "fp16"
+        need = max(P.dual_lds(c, epi_dw)[0] for c in (c1, c0))
+        assert (need <= P.dual_lds(c1, epi_dw)[1]) == row["fits"], (row["name"], need)
+        assert row["name"] in P.__doc__
+    assert [r["fits"] for r in P.DUAL] == [True, False]
+    for row in P.CHAIN_P:
+        assert CASE_BY_NAME[row["sa"]]["B"] == row["q"]["B"] and row["q"]["npxl"] == 4 and row["q"]["aff"] and row["name"] in P.__doc__
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", [r["name"] for r in P.DUAL])
+def test_gx_dual_matches_its_single_launch_references(gpu_device, monkeypatch, name):
+    from slide_amd import abi
+    row = [r for r in P.DUAL if r["name"] == name][0]
+    es = []
+    for cn in (row["m1"], row["m0"]):
+        c = CASE_BY_NAME[cn]
+        with monkeypatch.context() as mp:
+            for k, v in c["env"].items():
+                mp.setenv(k, v)
+            d = make_data(c)
+            es.append((c, d, _emit_gx(c, d, gpu_device)))
+    st = _run_pair(abi.OP_GEMM_GX_DUAL, es[0][2]["rows"], es[0][2]["m"].ops[-1], es[1][2]["m"].ops[-1])
+    assert st == 0, (name, st)
+    for c, d, e in es:
+        got, pad, stats = _read_gx(e)
+        _hold("%s / %s" % (name, c["name"]), "gemm_gx_dual_kernel<7>" if row["fits"] else c["kernel"], got, forward(c, d), pad, stats)
+
+
+def _emit_query(c, d, device):
+    """a 16-row fp16 GEMM of gemm_cases with an input affine, as the SA blocks' per-point query GEMM is emitted"""
+    import torch
+    import gemm_cases as G
+    from slide_amd import engine as E
+    B, K, N = c["B"], c["K"], c["N"]
+    assert c["prec"] == "fp16" and c["npxl"] == 4 and c["aff"] and not c["gn_fin"] and c["mode"] == G.EPI_NORM
+    assert c["addvec"] is None and not c["resid"] and c["pre_add"] is None and c["pair"] is None
+    m = _mini(B, "fp16", device)
+    m.use_cm = False  # (a per-point GEMM reads row-major weights)
+    rows, ld = B * 16, ru(K)
+    Xp = _alt((rows, ld), 3e4)
+    Xp[:, :K] = d["X"]
+    lay = E.gn_layout(N)
+    oidx, Np = lay[0], ru(lay[1])
+    out = torch.full((rows, Np), 7.0, dtype=torch.float16, device=device)
+    m.A.keep.append(out)
+    n_norm = G.gn_params(N)[1]
+    seg = dict(w=d["W"], bias=d["bias"], mode=c["mode"], out=out, layout=lay, gn=(d["gamma"][:n_norm], d["beta"][:n_norm]),
+               flags=(E.F_PRE_RELU if c["pre_relu"] else 0) | (E.F_POST_RELU if c["post_relu"] else 0))
+    sc, sh = np.ones((B, ld), np.float32), np.zeros((B, ld), np.float32)
+    sc[:, :K], sh[:, :K] = d["scale"], d["shift"]
+    m._gemm(m.A.put(Xp, m.adt), 4, [seg], in_affine=(m.A.put(sc), m.A.put(sh), 0, ld))
+    return m, out, oidx
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", [r["name"] for r in P.CHAIN_P])
+def test_sa_chain_p_matches_its_single_launch_references(gpu_device, name):
+    import gemm_cases as G
+    from slide_amd import abi
+    row = [r for r in P.CHAIN_P if r["name"] == name][0]
+    c, q = CASE_BY_NAME[row["sa"]], row["q"]
+    d, dq = make_data(c), G.make_data(q)
+    m, out = _emit_sa(c, d, gpu_device)
+    mq, outq, oidx = _emit_query(q, dq, gpu_device)
+    st = _run_pair(abi.OP_SA_CHAIN_P, c["B"], m.ops[-1], mq.ops[-1])
+    assert st == 0, (name, st)
+    _hold(name + " / " + c["name"], row["kernel"], _read_out(m, out, c["B"] * 256, c["chain"]["N"]), forward(c, d), np.zeros((1, 0)))
+    gq = outq.float().cpu().numpy()
+    _hold(name + " / " + q["name"], row["kernel"], gq[:, oidx], G.forward(q, dq), np.delete(gq, oidx, axis=1))

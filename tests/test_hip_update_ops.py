@@ -10,12 +10,11 @@ denoiser is involved.
   in-kernel noise             the Philox path of both kernels equals the explicit-noise path fed with slide_philox_normal_selftest's
                               output for the same (seed, nonce, step, global element offset); the self-test's output is within
                               NORMAL_BOUND of the float64 restatement, and on the CPU a generator with two counter words swapped is not."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import update_cases as uc
+from op_harness import Dev as _Dev, bits as _bits, run as _run
 from update_cases import C, F32, KDIM
 
 SEED = (0x9E3779B9, 0x7F4A7C15)  # (seed_lo, seed_hi): both above 2^31, so the words cross the int ABI as bit patterns
@@ -57,52 +56,6 @@ def test_feature_restatement_keeps_the_condition_and_skips_noise_at_t0():
 
 
 # ------------------------------------------------------------------------------------------------------------ GPU helpers
-class _Dev:
-    """device buffers of one update launch and its SlideOp"""
-
-    def __init__(self, device):
-        import torch
-        self.torch, self.device = torch, device
-        self.keep = []
-
-    def put(self, a):
-        t = self.torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
-        self.keep.append(t)
-        return t
-
-    def t_dev(self, t, step, nonce=0, offset=0):
-        return self.put(np.array([t, step, 0, uc.as_i32(nonce), offset, 0, 0, 0], np.int32))
-
-
-def _run(ops, times=1, graph=False):
-    """launches the ops `times` times back to back on one side stream with no host synchronisation in between"""
-    import torch
-    from slide_amd import _lib, abi
-    L = _lib.lib()
-    arr = (abi.SlideOp * len(ops))(*ops)
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    torch.cuda.synchronize()
-    with torch.cuda.stream(s):
-        if graph:
-            _lib.check(L.slide_graph_begin(s.cuda_stream), "graph_begin")
-            st = L.slide_run_ops(arr, len(ops), s.cuda_stream)
-            g = ctypes.c_void_p()
-            st2 = L.slide_graph_end(s.cuda_stream, ctypes.byref(g))
-            _lib.check(st, "slide_run_ops(capture)")
-            _lib.check(st2, "graph_end")
-            try:
-                for _ in range(times):
-                    _lib.check(L.slide_graph_launch(g, s.cuda_stream), "graph_launch")
-                s.synchronize()
-            finally:
-                L.slide_graph_destroy(g)
-        else:
-            for _ in range(times):
-                _lib.check(L.slide_run_ops(arr, len(ops), s.cuda_stream), "slide_run_ops")
-            s.synchronize()
-
-
 def _feat_op(d, x, eps, eps_ld, noise, t_dev, keypoint, tabs, clamp=0.0, cx0=None, kmask=None, feat0=None, ldf=0, half_out=0, copies=None,
              n_copies=0, seed=SEED):
     from slide_amd import abi
@@ -117,10 +70,6 @@ def _pos_op(d, x, eps, eps_ld, noise, t_dev, tabs, seed=SEED):
     p = lambda t: None if t is None else t.data_ptr()
     return abi.make_op(abi.OP_UPDATE_POS, i=(x.numel(), eps_ld, uc.as_i32(seed[0]), uc.as_i32(seed[1])),
                        p=(p(x), p(eps), p(noise), p(t_dev)) + tuple(p(t) for t in tabs))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == F32 else np.uint16)
 
 
 SENTINEL = 1234.5  # (exact in fp16 and fp32)
