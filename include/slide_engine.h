@@ -277,6 +277,15 @@ typedef struct SlidePointChainArgs {
   int32_t fuse_update;  /* 1: the launch also applies the feature DDPM's update (upd.kind == 1) to the state and advances the device-side
                          * timestep -- the lane that holds eps[row][channel] updates x[row][channel]; the noise of the workgroup's elements
                          * is drawn while the chain's loads are in flight.  Of `upd` the update members are read (kind ... copies). */
+  int32_t wpk_bytes;    /* 0: the row-major form above.  > 0: the PACKED form -- Wz points to ONE buffer of wpk_bytes bytes that holds every
+                         * weight of the chain, W2 / W0 / W1 and the four *_lo are NULL (anything else is refused).  The buffer holds the same
+                         * fp16 values per wave w (= channel block w of every layer) as 1 KB MFMA A-fragments in the order the kernel
+                         * consumes them; lane l owns bytes [16 l, 16 l + 16) of a fragment: the eight halves
+                         * W[32 w + (l & 31)][16 s + 8 (l >> 5) ..].  Wave w's slice, in fragments: for each s < kz/16: Wz rows 0..,
+                         * Wz rows 128.. (wide: then their two lo'); W2 s = 0..7 (wide: then W2_lo); W0 s < k0/16; W1 s = 0..7 when
+                         * w < n1c; wide: W0_lo, then W1_lo when w < n1c.  The four slices follow each other without gaps
+                         * (slide_amd/chain_pack.py packs and sizes them).  wpk_bytes must be the size (kz, k0, n1c) imply for the fp16
+                         * form, or twice that: the WIDE form.  (The field fills the padding in front of `upd`.) */
   SlideHeadArgs upd;
 } SlidePointChainArgs;
 

@@ -106,7 +106,8 @@ class SlideHeadArgs(ctypes.Structure):
 
 class SlidePointChainArgs(ctypes.Structure):
     _fields_ = (_fields(c_void_p, "Z Wz W2 W0 W1 vz v2 v0 b1 tvec t_idx cvec X eps Wz_lo W2_lo W0_lo W1_lo")
-                + _fields(c_int32, "rows z_ld kz x_ld k0 n1c eps_ld t_stride t_bs c_bs fuse_update") + [("upd", SlideHeadArgs)])
+                + _fields(c_int32, "rows z_ld kz x_ld k0 n1c eps_ld t_stride t_bs c_bs fuse_update wpk_bytes")
+                + [("upd", SlideHeadArgs)])
 
 
 class SlideOp(ctypes.Structure):

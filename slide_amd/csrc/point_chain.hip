@@ -17,6 +17,12 @@
 // planes x = xh + 2^-11 xl', three MFMAs per product (hi.xh into one accumulator set; hi.xl' + lo'.xh into a second, scaled by 2^-11
 // at the end) -- fp32-grade products; the input rows Z are fp16 as stored (exact: two MFMAs).  The lo fragments of the head's
 // weights are loaded after layer 1 (into the registers its weights leave).
+// PACKED (the engine's default, SLIDE_POINT_CHAIN_PACKED; SlidePointChainArgs.wpk_bytes): the same weights as ONE buffer of 1 KB fragments
+// in lane order, per wave in the order of use (slide_amd/chain_pack.py packs it once at plan time) -- and a prologue whose loads are all
+// unconditional and issued in the order [rows, vectors, half of layer 1 | t rows, rest of layer 1, layers 2 .. 4], so that every wait is
+// a counted vmcnt.  The row-major prologue below issues the weights first and the rows and vectors in loops behind them: the first
+// wait drains every weight, and each trip of those loops is a further serial L2 round trip (24.7 -> 14.8 us at 88 samples,
+// profiles/point_chain_packed.md).  The arithmetic is the same code: bit-identical outputs (tests/test_hip_point_chain_packed.py).
 // fuse_update (OPT-IN, SLIDE_POINT_CHAIN_UPDATE=1): the launch also applies the feature DDPM's update (update_feat_element,
 // ddpm_update.h) and advances the device-side timestep -- the lane that holds eps[row][channel] updates x[row][channel]; all 256
 // threads draw the workgroup's 32 x C normals into LDS right after issuing the chain's loads.  Measured slower than the separate
@@ -30,7 +36,7 @@ namespace {
 
 typedef SlidePointChainArgs ChainArgs;  // include/slide_engine.h
 
-template <int KZMAX, int K0MAX, bool WIDE>
+template <int KZMAX, int K0MAX, bool WIDE, bool PACKED>
 __global__ __launch_bounds__(256, 1) void point_chain_kernel(ChainArgs a) {
 #pragma clang fp contract(off)
   using T = _Float16;
@@ -51,6 +57,128 @@ __global__ __launch_bounds__(256, 1) void point_chain_kernel(ChainArgs a) {
   // ---- every global read of the chain, issued together
   f16x8 wz[2][KZMAX / 16], w2[8], w0[K0MAX / 16], w1[8];
   f16x8 wzl[2][WIDE ? KZMAX / 16 : 1], w2l[WIDE ? 8 : 1];  // WIDE: the low fragments of layers 1 and 2 (the head's follow after layer 1)
+  const uint32_t lane16 = lane * 16;
+  const GLOBAL_AS char *wpk_head = nullptr;  // PACKED: the wave's [W0_lo | W1_lo] fragments
+  if constexpr (PACKED) {
+    // PACKED (SlidePointChainArgs.wpk_bytes): a fragment is 1 KB in lane order and the wave's fragments lie in the order of their use, so
+    // every weight load is scalar base + lane * 16 (+ immediate) and reads 1 KB of consecutive memory (the row-major form reads 32 B
+    // from each of 32 rows: request-bound, tools/lds_fill.hip).  EVERY load below is issued unconditionally -- a slot past kz / past
+    // n1c reads the slice's first 16 bytes in all lanes (a broadcast) and nobody consumes it -- so the number of loads behind any one
+    // is a constant and the compiler's waits are counted (checked in hipcc -S): the rows and the vectors are waited for in front of
+    // the first barrier with the fragments in flight, layer 1 waits for its own step by step, layers 2 .. 4 land under it.
+    constexpr int LW = WIDE ? 4 : 2, N2 = WIDE ? 16 : 8, ZPT = KZMAX * 4 / 256;  // ZPT: 16-byte pieces of the 32 input rows per thread
+    static_assert((K0MAX - 128) * 4 <= 256 && ZPT * 256 == KZMAX * 4, "one piece of the head's extra columns per thread");
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+    const bool has1 = wave_s < a.n1c;
+    constexpr int NK0 = K0MAX / 16;  // (the launcher admits the packed form at k0 == K0MAX only)
+    const int o2 = nkz * LW, o1 = o2 + N2 + NK0, oh = o1 + (has1 ? 8 : 0), per_wave = o1 + (WIDE ? NK0 : 0);
+    const GLOBAL_AS char *wb = gptr<const char>((uint64_t)a.Wz) + ((size_t)(wave_s * per_wave + (has1 ? wave_s : a.n1c) * N2) << 10);
+    wpk_head = wb + ((size_t)oh << 10);
+    auto frag = [&](int f, bool live) __attribute__((always_inline)) {
+      const GLOBAL_AS char *p = wb + (live ? (size_t)f << 10 : (size_t)0);
+      return *(const GLOBAL_AS f16x8 *)(p + (live ? lane16 : 0u));
+    };
+    // ---- A: the timestep, the input rows, the head's [xyz | pad] columns, the vectors (all but the t rows)
+    const int trow = a.t_idx ? a.t_idx[0] : 0;
+    const int ppr = a.kz >> 3, ppx = (a.k0 - 128) >> 3, nsm = a.rows >> 4, smp0 = row0 >> 4;
+    u32x4 zr[ZPT], xr;
+    int zdst[ZPT];  // element offset into zs, or -1
+#pragma unroll
+    for (int j = 0; j < ZPT; ++j) {
+      const int i = tid + 256 * j;
+      const bool ok = i < 32 * ppr;
+      const int ii = ok ? i : 0, r = ii / ppr, pc = ii - r * ppr;
+      int grow = row0 + r;
+      grow = grow < a.rows ? grow : a.rows - 1;
+      zr[j] = *(const GLOBAL_AS u32x4 *)(gptr<const T>((uint64_t)a.Z) + (size_t)grow * a.z_ld + pc * 8);
+      zdst[j] = ok ? r * LDZ + pc * 8 : -1;
+    }
+    int xdst;
+    {
+      const bool ok = tid < 32 * ppx;
+      const int ii = ok ? tid : 0, r = ii / ppx, pc = ii - r * ppx;
+      int grow = row0 + r;
+      grow = grow < a.rows ? grow : a.rows - 1;
+      xr = *(const GLOBAL_AS u32x4 *)(gptr<const T>((uint64_t)a.X) + (size_t)grow * a.x_ld + 128 + pc * 8);
+      xdst = ok ? r * LDX + 128 + pc * 8 : -1;
+    }
+    // vl[i], i = tid + 256 j, from the sources of the row-major form's loop, as selects between ADDRESSES (no control flow in front of
+    // a load); a missing source reads vz[0] and stores 0.  j == 2 is exactly the two t rows (vl[512 .. 768)): they follow in C.
+    float vr[8];
+    bool vok[8];
+    {
+      const uint64_t pvz = (uint64_t)a.vz, pv2 = (uint64_t)a.v2, pv0 = (uint64_t)a.v0, pb1 = (uint64_t)a.b1, pcv = (uint64_t)a.cvec;
+      const bool lo128 = tid < 128, hc = pcv != 0, hb = tid < a.n1c * 32;
+      const int s0 = smp0 < nsm ? smp0 : nsm - 1, s1 = smp0 + 1 < nsm ? smp0 + 1 : nsm - 1;
+      const uint64_t c0 = hc ? pcv + 4 * ((uint64_t)s0 * a.c_bs + (tid & 127)) : pvz;  // the class row of the workgroup's first sample,
+      const uint64_t c1 = hc ? pcv + 4 * ((uint64_t)s1 * a.c_bs + (tid & 127)) : pvz;  // ... of its second
+      const uint64_t src[8] = {pvz + 4 * tid, pvz + 4 * (tid + 256), 0, pv2 + 4 * tid, lo128 ? pv2 + 4 * (tid + 256) : c0,
+                               lo128 ? c1 : pv0 + 4 * (tid - 128), pv0 + 4 * (tid + 128), hb ? pb1 + 4 * tid : pvz};
+      const bool okj[8] = {true, true, false, true, lo128 || hc, !lo128 || hc, true, hb};
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (j != 2) {
+          vr[j] = *gptr<const float>(src[j]);
+          vok[j] = okj[j];
+        }
+    }
+    // ... and the first half of layer 1's fragments: enough in flight to cover B's wait, and B frees its registers for the rest
+    auto issue_l1 = [&](int s2) __attribute__((always_inline)) {
+      const bool live = s2 < nkz;
+      wz[0][s2] = frag(s2 * LW, live);
+      wz[1][s2] = frag(s2 * LW + 1, live);
+      if constexpr (WIDE) {
+        wzl[0][s2] = frag(s2 * LW + 2, live);
+        wzl[1][s2] = frag(s2 * LW + 3, live);
+      }
+    };
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s2 = 0; s2 < KZMAX / 32; ++s2) issue_l1(s2);
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- B: what A's first loads brought goes to LDS; the fragments stay in flight
+#pragma unroll
+    for (int j = 0; j < ZPT; ++j)
+      if (zdst[j] >= 0) *reinterpret_cast<u32x4 *>(zs + zdst[j]) = zr[j];
+    if (xdst >= 0) {
+      *reinterpret_cast<u32x4 *>(xs + xdst) = xr;
+      if constexpr (WIDE) *reinterpret_cast<u32x4 *>(xs_lo + xdst) = u32x4{0, 0, 0, 0};  // (fp16 as stored: exact)
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (j != 2 && tid + 256 * j < NVL) vl[tid + 256 * j] = vok[j] ? vr[j] : 0.f;
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- C: the t rows (row t of the per-timestep table, or the samples' own rows), the rest of layer 1, the fragments of layers 2 .. 4
+    float tv;
+    {
+      int sm = smp0 + (tid >> 7);
+      sm = sm < nsm ? sm : nsm - 1;
+      const uint64_t pt = (uint64_t)a.tvec;
+      tv = *gptr<const float>(pt ? pt + 4 * ((a.t_idx ? (uint64_t)trow * a.t_stride : 0) + (uint64_t)sm * a.t_bs + (tid & 127)) : (uint64_t)a.vz);
+    }
+#pragma unroll
+    for (int s2 = KZMAX / 32; s2 < KZMAX / 16; ++s2) issue_l1(s2);
+    {
+      // [W2 | W2_lo | W0] are consecutive: scalar bases, the lane's 16 bytes as the one vector offset
+      const GLOBAL_AS char *b2 = wb + ((size_t)o2 << 10);
+#pragma unroll
+      for (int s2 = 0; s2 < 8; ++s2) w2[s2] = *(const GLOBAL_AS f16x8 *)(b2 + s2 * 1024 + lane16);
+      if constexpr (WIDE) {
+#pragma unroll
+        for (int s2 = 0; s2 < 8; ++s2) w2l[s2] = *(const GLOBAL_AS f16x8 *)(b2 + (8 + s2) * 1024 + lane16);
+      }
+#pragma unroll
+      for (int s2 = 0; s2 < NK0; ++s2) w0[s2] = *(const GLOBAL_AS f16x8 *)(b2 + (N2 + s2) * 1024 + lane16);
+      // W1: waves past n1c own none -- their eight loads read the slice's first bytes in all lanes
+      const GLOBAL_AS char *b1 = wb + (has1 ? ((size_t)o1 << 10) : (size_t)0);
+      const uint32_t vo1 = has1 ? lane16 : 0u;
+#pragma unroll
+      for (int s2 = 0; s2 < 8; ++s2) w1[s2] = *(const GLOBAL_AS f16x8 *)(b1 + (has1 ? s2 * 1024 : 0) + vo1);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- D: the t rows to LDS; behind the barrier layer 1 waits for its fragments one step at a time, with layers 2 .. 4 in flight
+    vl[512 + tid] = a.tvec ? tv : 0.f;
+  } else {
   if constexpr (WIDE) {
     const GLOBAL_AS T *wp = gptr<const T>((uint64_t)a.Wz_lo) + (size_t)(wave * 32 + col) * a.kz + half * 8;
 #pragma unroll
@@ -120,6 +248,7 @@ __global__ __launch_bounds__(256, 1) void point_chain_kernel(ChainArgs a) {
       vl[i] = v;
     }
   }
+  }  // (!PACKED)
   // the update's noise, drawn while the loads above are in flight: z[row][channel] of the workgroup's rows (t > 0, channels past the key points)
   __shared__ float zl[32 * 64];
   int ut = 0, ustep = 0;
@@ -224,7 +353,15 @@ __global__ __launch_bounds__(256, 1) void point_chain_kernel(ChainArgs a) {
   }
   // WIDE: the head's low fragments, loaded now (the registers of layer 1's weights are free); they land under layer 2
   f16x8 w0l[WIDE ? K0MAX / 16 : 1], w1l[WIDE ? 8 : 1];
-  if constexpr (WIDE) {
+  if constexpr (WIDE && PACKED) {
+    __builtin_amdgcn_sched_barrier(0);  // (not hoisted into layer 1: they take the registers its fragments leave)
+    const bool has1 = __builtin_amdgcn_readfirstlane(wave) < a.n1c;
+    const uint32_t vo1 = has1 ? lane16 : 0u;
+#pragma unroll
+    for (int s2 = 0; s2 < K0MAX / 16; ++s2) w0l[s2] = *(const GLOBAL_AS f16x8 *)(wpk_head + s2 * 1024 + lane16);
+#pragma unroll
+    for (int s2 = 0; s2 < 8; ++s2) w1l[s2] = *(const GLOBAL_AS f16x8 *)(wpk_head + (has1 ? (K0MAX / 16 + s2) * 1024 : 0) + vo1);
+  } else if constexpr (WIDE) {
     const GLOBAL_AS T *w0p = gptr<const T>((uint64_t)a.W0_lo) + (size_t)(wave * 32 + col) * a.k0 + half * 8;
 #pragma unroll
     for (int s2 = 0; s2 < K0MAX / 16; ++s2)
@@ -350,14 +487,27 @@ int slide_launch_point_chain(const SlideOp &o, hipStream_t s) {
   const SlidePointChainArgs *h = (const SlidePointChainArgs *)o.p[0];
   if (!h || h->rows <= 0 || h->rows % 16 || h->kz % 32 || h->kz <= 0 || h->kz > 192 || h->z_ld < h->kz || h->z_ld % 8 || h->k0 % 32 ||
       h->k0 <= 128 || h->k0 > 160 || h->x_ld < h->k0 || h->x_ld % 8 || (h->n1c != 1 && h->n1c != 2) || h->eps_ld % 4 ||
-      h->eps_ld > 32 * h->n1c || h->t_bs < 0 || !h->Z || !h->Wz || !h->W2 || !h->W0 || !h->W1 || !h->vz || !h->v2 || !h->v0 || !h->b1 || !h->X || (!h->eps && !h->fuse_update))
+      h->eps_ld > 32 * h->n1c || h->t_bs < 0 || !h->Z || !h->Wz || !h->vz || !h->v2 || !h->v0 || !h->b1 || !h->X || (!h->eps && !h->fuse_update))
     return -3;
   if (h->fuse_update && (h->upd.kind != 1 || h->upd.C > 32 * h->n1c || h->upd.C > 64 || !h->upd.x || !h->upd.t_dev || !h->upd.t0 || !h->upd.t1 ||
                          !h->upd.t2 || !h->upd.t3 || !h->upd.t4 || (h->upd.kdim > 0 && !h->upd.keypoint)))
     return -3;
+  const dim3 grid((h->rows + 31) / 32);
+  if (h->wpk_bytes) {
+    // the packed form: ONE buffer at Wz, of the size the shapes imply (fp16 form) or twice that (WIDE); no row-major pointer beside it
+    const int frags = 4 * (2 * (h->kz / 16) + 8 + h->k0 / 16) + 8 * h->n1c;
+    const bool wide = h->wpk_bytes == 2048 * frags;
+    if ((!wide && h->wpk_bytes != 1024 * frags) || h->k0 != 160 || ((uintptr_t)h->Wz & 15) || h->W2 || h->W0 || h->W1 || h->Wz_lo || h->W2_lo || h->W0_lo ||
+        h->W1_lo)
+      return -3;
+    if (wide) hipLaunchKernelGGL((point_chain_kernel<192, 160, true, true>), grid, dim3(256), 0, s, *h);
+    else hipLaunchKernelGGL((point_chain_kernel<192, 160, false, true>), grid, dim3(256), 0, s, *h);
+    return (int)hipGetLastError();
+  }
+  if (!h->W2 || !h->W0 || !h->W1) return -3;
   const bool wide = h->Wz_lo || h->W2_lo || h->W0_lo || h->W1_lo;
   if (wide && !(h->Wz_lo && h->W2_lo && h->W0_lo && h->W1_lo)) return -3;
-  if (wide) hipLaunchKernelGGL((point_chain_kernel<192, 160, true>), dim3((h->rows + 31) / 32), dim3(256), 0, s, *h);
-  else hipLaunchKernelGGL((point_chain_kernel<192, 160, false>), dim3((h->rows + 31) / 32), dim3(256), 0, s, *h);
+  if (wide) hipLaunchKernelGGL((point_chain_kernel<192, 160, true, false>), grid, dim3(256), 0, s, *h);
+  else hipLaunchKernelGGL((point_chain_kernel<192, 160, false, false>), grid, dim3(256), 0, s, *h);
   return (int)hipGetLastError();
 }

@@ -15,7 +15,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import knobs
+from . import chain_pack, knobs
 from ._lib import SlideHipError, check, lib
 # the C side of include/slide_engine.h -- every OP_* / EPI_* / F_* constant, PREC, the struct mirrors, make_op and ru -- is declared
 # in abi.py; all of it stays importable from this module
@@ -1470,8 +1470,16 @@ class DenoiserEngine:
             def lo(w):
                 w = np.asarray(w, np.float32)
                 return ((w - w.astype(np.float16).astype(np.float32)) * np.float32(2048.0)).astype(np.float32)
-            d.update(Wz_lo=A.put(lo(Wz), torch.float16), W2_lo=A.put(lo(W2), torch.float16), W0_lo=A.put(lo(W0), torch.float16),
-                     W1_lo=A.put(lo(W1), torch.float16))
+            los = [lo(w) for w in (Wz, W2, W0, W1)]
+            d.update(Wz_lo=A.put(los[0], torch.float16), W2_lo=A.put(los[1], torch.float16), W0_lo=A.put(los[2], torch.float16),
+                     W1_lo=A.put(los[3], torch.float16))
+        else:
+            los = None
+        # the same fp16 values once more as ONE buffer of MFMA fragments in the order the kernel consumes them (chain_pack.py): the
+        # launch then reads 1 KB of consecutive memory per load instruction.  The weights are fixed for the life of the engine, so
+        # this is plan-time work.  SLIDE_POINT_CHAIN_PACKED=0: the row-major launch (A/B).
+        if self.knobs.SLIDE_POINT_CHAIN_PACKED:
+            d["Wpk"] = A.put(chain_pack.pack(Wz, W2, W0, W1, los))
         return d
 
     def point_chain_args(self, eps_out=None):
@@ -1481,9 +1489,12 @@ class DenoiserEngine:
         if pch is None:
             return None
         c = SlidePointChainArgs()
-        for k_ in ("Z", "Wz", "W2", "W0", "W1", "vz", "v2", "v0", "b1", "X", "Wz_lo", "W2_lo", "W0_lo", "W1_lo"):
+        packed = "Wpk" in pch  # (then Wz is the packed buffer and the other seven weight pointers stay NULL)
+        for k_ in ("Z", "vz", "v2", "v0", "b1", "X") + (() if packed else ("Wz", "W2", "W0", "W1", "Wz_lo", "W2_lo", "W0_lo", "W1_lo")):
             if k_ in pch:
                 setattr(c, k_, pch[k_].data_ptr())
+        if packed:
+            c.Wz, c.wpk_bytes = pch["Wpk"].data_ptr(), pch["Wpk"].numel() * 2
         c.eps = (eps_out if eps_out is not None else self.eps_pad).data_ptr()
         c.rows, c.z_ld, c.kz, c.x_ld, c.k0, c.n1c = self.B * 16, pch["Z"].shape[1], pch["kz"], pch["X"].shape[1], pch["k0"], pch["n1c"]
         c.eps_ld = self.eps_pad.shape[1]

@@ -80,6 +80,7 @@ TABLE = _table("plan", [
     ("SLIDE_PP", "flag", "0", "split plans: runs of 16-row launches as one per-point stage launch"),
     ("SLIDE_POINT_CHAIN", "flag", "1", "FP0's second Mlp + the output head offered to the samplers as one launch (0: four launches)"),
     ("SLIDE_POINT_CHAIN_WIDE", "flag", "1", "the point chain in the split arithmetic (0: fp16 operands)"),
+    ("SLIDE_POINT_CHAIN_PACKED", "flag", "1", "the point chain reads its weights as one buffer of packed MFMA fragments (0: row-major)"),
     # diffusion.py
     ("SLIDE_FUSE_PREP", "flag", "1", "feature sampler: point preparation once per chain (0: one launch per step)"),
     ("SLIDE_HEAD_UPDATE", "flag", "0", "output head + DDPM update in one launch"),

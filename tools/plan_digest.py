@@ -28,7 +28,8 @@ KNOBS = ["", "SLIDE_GX=0", "SLIDE_GXS=0", "SLIDE_CM=0", "SLIDE_GLDS=0", "SLIDE_P
          "SLIDE_GXS_CHAIN=0", "SLIDE_MERGE_Q=0", "SLIDE_POINT_CHAIN=0", "SLIDE_TWO_LANES=1", "SLIDE_PERSISTENT=1",
          "SLIDE_POINT_CHAIN_WIDE=0", "SLIDE_GLDS_WIDE=1 SLIDE_GATHER=0", "SLIDE_CBW4_TILES=1", "SLIDE_CBW1_TILES=8", "SLIDE_TAIL_OCC3=1",
          "SLIDE_TAIL_WIDE=4", "SLIDE_TAIL_WIDE=1000", "SLIDE_TAIL8=1", "SLIDE_TAIL_RX=0", "SLIDE_STAGGER_US=0.07", "SLIDE_BODY=2",
-         "SLIDE_GX=0 SLIDE_XS=auto SLIDE_XS_CBW=4", "SLIDE_GX=0 SLIDE_XS=auto SLIDE_XS_OCC=2", "SLIDE_PERSISTENT=2"]
+         "SLIDE_GX=0 SLIDE_XS=auto SLIDE_XS_CBW=4", "SLIDE_GX=0 SLIDE_XS=auto SLIDE_XS_OCC=2", "SLIDE_PERSISTENT=2",
+         "SLIDE_POINT_CHAIN_PACKED=0"]
 
 
 def matrix():
