@@ -103,7 +103,9 @@ enum {
   SLIDE_OP_UPDATE_FEAT = 11,/* p: x, eps, noise(or NULL), t_dev, keypoint, c_recip, c_recipm1, c1, c2, c_std, [10] complete_x0 (n_pts*C) + [11] keypoint_mask (n_pts) of the local re-sampling mode (both NULL = off), [12] per-point table feat0 [n_pts][i[6]] (fp16 if i[7]) or NULL + [13] SlidePrepCopy[i[8]]: with fixed key points the update also writes the feature columns SLIDE_OP_PREP_POINTS would derive from the new state (the preparation then runs once per chain, not per step)  i: n_pts, C, kdim, seed_lo, seed_hi, eps_ld (0 = C), ldf, feat0 is fp16, n_copies  f: clamp.  In-kernel noise is keyed on (seed, t_dev[3] = chain nonce, t_dev[1] = step, GLOBAL element = element + t_dev[4] * elements per sample; t_dev[4] = global index of the chain's first sample) */
   SLIDE_OP_ADVANCE_T = 12,  /* p: t_dev  (t_dev[0] -= 1; t_dev[1] += 1); t_dev = [t, step, blocks-done counter, chain nonce, global index of the first sample, 3 spare] (8 ints) */
   SLIDE_OP_SYNC = 14,       /* i: from_lane, to_lane -- lane `to` waits for everything issued so far on lane `from` */
-  SLIDE_OP_GROUPNORM_NCHW = 13,/* p: x, gamma, beta, y (NCHW fp32)   i: B, C, HW, G, n_norm, relu  (module-level path) */
+  SLIDE_OP_GROUPNORM_NCHW = 13,/* p: x, gamma, beta, y (NCHW fp32)   i: B, C, HW, G, n_norm, relu  (module-level path):
+                                * channels [0, n_norm) in G groups, the rest copied (ReLU'd).  B, C, HW, G >= 1, B <= 65535, 0 < n_norm <= C,
+                                * n_norm % G == 0, all four pointers set: else -3, nothing launched */
   SLIDE_OP_ATTN_TAIL = 16,  /* fp16: scores GEMM + values GEMM (GroupNorm, ReLU) + softmax-weighted sum over the neighbours in one launch.  p: u, W5, mo, Wv, out, vec [bias_s | bias_v | gamma | beta][n_cob*32], [6] optional chunk-major copy of out [c/32][points][32] (a gather table of the next block: SLIDE_OP_GEMM f[2] == 32 reads p[8] that way), [7] optional copy of the first f[3] channels into another per-point buffer with leading dimension f[2]   i: rows, u_ld, k1, mo_ld, k2, n_cob, npx_log2, gs, n_norm, out_ld   f: 1 / (gs * rows per sample), [1] bit 0: both weight matrices chunk-major [k/32][n_cob*32][32] (u / mo are chunk-major [k/32][rows][32] when their ld is 32), bit 1: the two-stage-ring form at three workgroups per CU, bit 3 (round 5, csrc/gemm_gxs.hip attn_tail_split_kernel): SPLIT arithmetic -- u, mo and out are FLOAT rows, both weight matrices float row-major [n_cob*32][k], every contraction as two-term fp16 operand splits on one accumulator set (|w| < 32 required), bit 4 (round 6): u and mo are FRAGMENT-major (SLIDE_F_OUT_FM; register-X kernel only: the launcher refuses other forms) */
   SLIDE_OP_GEMM_GX = 17,    /* fp16 "generated-X" GEMM of the pair decomposition (gemm_gx.hip): the first layer of an SA / FP
                              * block is linear in [neighbour features | coordinates], so its output for row (point p, slot j) is ta[q] + tb[p]
@@ -180,14 +182,17 @@ enum {
                              * [6] out fp16 [rows / K][ldo], [7] counts int32 [rows / K] or NULL, [8] vss fp32 [sample][2][ldv] (deferred
                              * normalisation of V) or NULL, [11] add vectors of X's deferred step.  i: rows, x_ld, k_pad, n_cob, K (4 | 8 | 16 | 32),
                              * in_bs, ldv, ldo, points per sample, ReLU after V's affine, C (logical channels).  f: [1] 256-row tiles per sample,
-                             * [2] add_bs, [3] 2 * add_n + relu (X's deferred step, as SLIDE_OP_GEMM) */
+                             * [2] add_bs, [3] 2 * add_n + relu (X's deferred step, as SLIDE_OP_GEMM).  rows % K == 0; a ragged last tile is
+                             * served WITHOUT the input affine only: with in_scale the tile index selects the sample (tile / tiles per sample), so
+                             * rows must be a multiple of 256 * max(1, tiles per sample) -- anything else is refused with -3, nothing launched */
   SLIDE_OP_HEAD_UPDATE = 33,/* output head (two per-point GEMMs with the GroupNorm between them) + DDPM update + device-side t -= 1 as one launch
                              * (csrc/engine.hip head_update_kernel): p[0] = HOST pointer to a SlideHeadArgs block */
   SLIDE_OP_BLOCK_BODY = 30, /* the whole K-expanded body of an SA / FP block whose widths are <= 256 channels in one launch (csrc/block_body.hip):
                              * Mlp tail -> mo, generated keys -> u, attention tail; one workgroup per sample, mo / u as MFMA operand fragments in
                              * registers, weights through one LDS-DMA ring.  p[0]: HOST pointer to the BodyArgs block (csrc/block_body.hip;
                              * its members are device pointers), kept alive by the plan.  i: npx_log2 (7 | 8), has_rest_mlp */
-  SLIDE_OP_TRANSPOSE = 15,  /* p: in, out (fp32)   i: B, R, C, in_ld, out_ld, in_batch_stride, out_batch_stride, out_is_fp16: out[b][c][r] = in[b][r][c] (module-level path: NCHW <-> row-major) */
+  SLIDE_OP_TRANSPOSE = 15,  /* p: in, out (fp32)   i: B, R, C, in_ld, out_ld, in_batch_stride, out_batch_stride, out_is_fp16: out[b][c][r] = in[b][r][c] (module-level path: NCHW <-> row-major).
+                             * B, R, C >= 1, B <= 65535, R <= 32 * 65535, in_ld >= C, out_ld >= R, both pointers set: else -3, nothing launched */
   /* Row-major module-level path (rows_ops.hip): an activation is [B * S][ld] (S rows per sample, ld = channels rounded up
    * to 32, pad columns zero), fp32 or -- i[9] = 1 -- fp16.  Replaces the reference's NCHW tensor program of
    * Mlp_plus_t_emb / AttentionModule / QueryAndGroup('nn') / group_knn (pointnet2_modules.py:71-176, attention.py:35-96,

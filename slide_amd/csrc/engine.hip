@@ -829,7 +829,11 @@ int run_op(const SlideOp &o, hipStream_t s) {
 #else
       return SLIDE_ST_EXPERIMENT;  // (opt-in since round 5: block_body.hip is part of the experiments build)
 #endif
-    case SLIDE_OP_TRANSPOSE:
+    case SLIDE_OP_TRANSPOSE:  // i: B, R, C, in_ld, out_ld, in_batch_stride, out_batch_stride, out_is_fp16   p: in, out
+      // (an empty or oversized grid is a launch error; a leading dimension below the row length overlaps rows)
+      if (o.i[0] <= 0 || o.i[0] > 65535 || o.i[1] <= 0 || (o.i[1] + 31) / 32 > 65535 || o.i[2] <= 0 || o.i[3] < o.i[2] || o.i[4] < o.i[1] ||
+          !o.p[0] || !o.p[1])
+        return -3;
       if (o.i[7])  // fp16 destination (module-level throughput mode)
         hipLaunchKernelGGL(transpose_kernel<_Float16>, dim3((o.i[2] + 31) / 32, (o.i[1] + 31) / 32, o.i[0]), dim3(256), 0, s,
                            o.i[1], o.i[2], o.i[3], o.i[4], (long long)o.i[5], (long long)o.i[6], (const float *)o.p[0],
@@ -840,6 +844,10 @@ int run_op(const SlideOp &o, hipStream_t s) {
                            (float *)o.p[1]);
       break;
     case SLIDE_OP_GROUPNORM_NCHW:  // i: B, C, HW, G, n_norm, relu   p: x, gamma, beta, y
+      // (G = 0 divides by zero on the device; n_norm % G != 0 or n_norm > C normalises a span that is not the groups')
+      if (o.i[0] <= 0 || o.i[0] > 65535 || o.i[1] <= 0 || o.i[2] <= 0 || o.i[3] < 1 || o.i[4] <= 0 || o.i[4] > o.i[1] || o.i[4] % o.i[3] ||
+          !o.p[0] || !o.p[1] || !o.p[2] || !o.p[3])
+        return -3;
       hipLaunchKernelGGL(group_norm_nchw_kernel, dim3(o.i[3] + (o.i[4] < o.i[1] ? 1 : 0), o.i[0]), dim3(256), 0, s, o.i[1],
                          o.i[2], o.i[3], o.i[4], o.i[5], (const float *)o.p[0], (const float *)o.p[1],
                          (const float *)o.p[2], (float *)o.p[3]);

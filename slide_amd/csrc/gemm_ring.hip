@@ -866,6 +866,9 @@ int run_gemm_attend(const SlideOp &o, hipStream_t s) {
   if (a.at_klog2 < 0 || a.rows <= 0 || a.rows % K || a.k_pad % BK || a.x_ld % 8 || a.n_cob <= 0 || !a.X || !a.W || !a.epi || !a.at_V ||
       !a.at_out || a.at_ldv % 4 || a.at_ldo % 4 || a.at_ldv < a.n_cob * 32 || a.at_ldo < a.n_cob * 32 || (a.in_scale && !a.in_shift))
     return -3;
+  // input affine: the kernel takes the sample of a tile from the tile index (tile / aff_tps, clamped to rows / 256 / aff_tps - 1) --
+  // whole tiles and whole samples only (fewer rows than one sample's tiles would clamp to sample -1)
+  if (a.in_scale && a.rows % ((long long)TM * a.aff_tps)) return -3;
   return a.in_scale ? launch_gemm_attend<true>(a, s) : launch_gemm_attend<false>(a, s);
 }
 

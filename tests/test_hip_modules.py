@@ -639,7 +639,8 @@ def test_attention_fused_score_gemm_and_attend(gpu_device, monkeypatch, npnt, K)
     of the values as ONE launch (SLIDE_OP_GEMM_ATTEND: the score map stays in the accumulators) against the two-launch form
     (SLIDE_MODULE_FUSE_ATTEND=0: scores stored in fp16, rows_attn_kernel) and an fp64 restatement of attention.py:70-96, with and
     without ball-query counts.  The fused form soft-maxes fp32 scores, the two-launch form fp16-rounded ones: they agree to <= 3e-3
-    relative L2 and the fused form is not further from the restatement than the two-launch form (+ 10 %)."""
+    relative L2 and the fused form is not further from the restatement than the two-launch form (+ 10 %).
+    (The launch itself, elementwise against float64 at every argument form: tests/test_hip_attend.py.)"""
     from pointnet2_ops.attention import AttentionModule
     monkeypatch.setenv("SLIDE_MODULE_PREC", "fp16")
     d = gpu_device
