@@ -238,6 +238,47 @@ SLIDE_API int slide_mc_count(int b, int r, const float *phi, float level, int *c
 SLIDE_API int slide_mc_emit(int b, int r, const float *phi, float level, const int *counts_ws, const long long *totals, float *verts,
                             float *normals, int *faces, int *ws, slide_stream_t stream);
 
+/* ------------------------------------------------------------------ Part 7: area-weighted point samples from triangle meshes */
+/* A batch of b meshes is PACKED, as the marching cubes above leave it: verts (sum V, 3) f32, faces (sum F, 3) int32 with vertex
+ * indices LOCAL to the mesh, optional vertex normals (sum V, 3) f32, voff / foff (b + 1) int64 = every mesh's first row in verts /
+ * faces, non-decreasing, voff[b] = sum V, foff[b] = sum F.  fp32 with contraction off unless it says double or integer
+ * (csrc/mesh_sample.hip writes the same definition out with the launch structure):
+ *
+ *   n_f = (v1 - v0) x (v2 - v0), each component a*b - c*d as two products and one subtraction;
+ *   area_f = 0.5f * sqrtf(n.n) with n.n = (nx*nx + ny*ny) + nz*nz;  amax = the largest finite area of the mesh;
+ *   q_f = (uint64) floor((double)area_f * 2^32 / (double)amax), 0 for a zero or non-finite area or amax = 0;
+ *   cdf_f = q_0 + ... + q_f within the mesh (inclusive, uint64, exact in any order);  total = cdf_{F-1} < 2^63.
+ *   Faces smaller than amax 2^-32 are never drawn: the only bias.
+ *
+ * Sample s of mesh m takes four 32-bit words (c0, c1, c2, c3): the caller's `words`, or one Philox4x32-10 call with key
+ * (seed_lo, seed_hi) and counter (s, mesh_id[m], stream_id, 0x13198A2E) (slide_philox_normal_selftest's constant is 0x85A308D3):
+ *
+ *   r = c0 << 32 | c1;  t = mulhi64(r, total) in [0, total);  face = the number of cdf entries <= t (a face with q = 0 is never chosen);
+ *   u = ((float)(c2 >> 8) + 0.5f) * 2^-24, v likewise from c3 (the uniform of philox_normal; in (0, 1]);
+ *   su = sqrtf(u), w0 = 1 - su, w1 = su * (1 - v), w2 = su * v (pytorch3d's weights);  p = (w0*v0 + w1*v1) + w2*v2;
+ *   normal = n_f / max(|n_f|, FLT_EPSILON), or with vertex_normals g / max(|g|, FLT_EPSILON), g = (w0*g0 + w1*g1) + w2*g2.
+ *
+ * A mesh's samples depend on (mesh, seed, mesh_id, stream_id, s) alone: not on b, the mesh's position or a chunking of the batch.
+ * Both entry points return -2 for a negative count or a NULL array before any launch, and 0 without a launch for b = 0 (and for
+ * sum F = 0 / s = 0).
+ *
+ * The spans of the cdf scan, in faces: level 0 one thread, 1 one wave, 2 one pass of a mesh's workgroup; -2 otherwise. */
+SLIDE_API int slide_mesh_cdf_span(int level);
+/* areas (sum F) f32 and cdf (sum F) uint64, nf = sum F <= 2^31 - 1.  A face with a vertex index outside [0, V) of its mesh -- tested
+ * BEFORE it is used -- sets flag |= 1, one with a non-finite coordinate flag |= 2 (flag (1) int32, zero-filled by the caller); either
+ * gets area 0, hence q = 0.  Two launches: a thread per face, then one workgroup per mesh (maximum, quantise, scan). */
+SLIDE_API int slide_mesh_face_cdf(int b, long long nf, const float *verts, const int *faces, const long long *voff,
+                                  const long long *foff, float *areas, unsigned long long *cdf, int *flag, slide_stream_t stream);
+/* s samples per mesh with cdf as slide_mesh_face_cdf left it (same arrays): points (b,s,3) f32, valid (b) int32, and when not NULL
+ * normals (b,s,3) f32 and face_idx (b,s) int32 (the face's row WITHIN its mesh).  mesh_ids (b) int32 or NULL (mesh m gets m); words
+ * (b,s,4) uint32, 16-byte aligned, or NULL (Philox); seed_lo, seed_hi, stream_id carry the bit patterns of unsigned words.
+ * vertex_normals != 0 needs vnormals and normals.  A mesh without faces or with total = 0 gets points = normals = 0, face_idx = -1
+ * and valid = 0 (else 1).  One launch, a thread per sample; b <= 65535. */
+SLIDE_API int slide_mesh_sample(int b, int s, const float *verts, const int *faces, const float *vnormals, const long long *voff,
+                                const long long *foff, const unsigned long long *cdf, int seed_lo, int seed_hi, int stream_id,
+                                const int *mesh_ids, const unsigned *words, int vertex_normals, float *points, float *normals,
+                                int *face_idx, int *valid, slide_stream_t stream);
+
 /* ------------------------------------------------------------------ Part 3: denoiser engine */
 /* see slide_engine.h */
 SLIDE_API const char *slide_hip_version(void);

@@ -1,7 +1,7 @@
 """Point clouds -> DPSR indicator grids: the coordinate transformations of the reference's pointnet2/dpsr_evaluation.py
 (shapenet_psr_normalize lines 22-32, compute_center_and_max_length 34-43, the tail of network_output_to_dpsr_grid 77-86), and DPSR
-grids -> meshes on disk (batch_mc_from_psr 291-340).  The refine-and-upsample network in front of them and the evaluation loop behind
-them are not part of this build."""
+grids -> meshes on disk and the point sets sampled from them (batch_mc_from_psr 291-340).  The refine-and-upsample network in front of
+them and the evaluation loop behind them are not part of this build."""
 import os
 
 import numpy as np
@@ -35,16 +35,27 @@ def points_to_dpsr_grid(points, normals, dpsr, scale=1, explicit_normalize=False
 
 
 def batch_mc_from_psr(psr_grid, save_dir, save_prefix, batch_info=None, start_idx=0, sample_points_from_mesh=False,
-                      return_original_scale=False, original_center=None, original_max_length=None):
+                      return_original_scale=False, original_center=None, original_max_length=None, seed=0, num_samples=2048,
+                      num_dense=20480):
     """marching cubes of psr_grid (B, res, res, res) and one PLY per shape: <save_prefix>_<start_idx + i:05d>.ply under save_dir (or
     <batch_info[i]>_<...>.ply).  The vertices are in [0, 1) (divided by res); with return_original_scale the mesh's bounding box is
-    mapped to original_center (B, 1, 3) and original_max_length (B, 1, 1).  Returns the reference's four lists, which only its
-    sample_points_from_mesh fills: that path (pytorch3d's sample_points_from_meshes + FPS) is not part of this build."""
+    mapped to original_center (B, 1, 3) and original_max_length (B, 1, 1).  Returns the reference's four results; they are empty
+    lists unless sample_points_from_mesh is set (CUDA grids only), and then numpy arrays (B, num_samples, 3) float32:
+
+      points, normals                  num_samples area-weighted samples of every mesh as written to disk, with unit face normals
+                                       (slide_amd.mesh.sample_points_from_meshes, noise stream 0)
+      uniform points, uniform normals  num_dense samples (noise stream 1) reduced to num_samples by farthest point sampling from
+                                       sample 0 -- the samples are i.i.d., so that is a random point -- and their normals
+
+    One sampling call serves the batch.  Mesh i draws with the id start_idx + i under `seed`: a shape's samples do not depend on
+    how the shapes are split into batches.  (The reference samples with torch's global generator, one mesh at a time, and starts
+    the farthest point sampling at a random index.)"""
     from dpsr_utils.io_utils import save_mesh
     from dpsr_utils.utils import mc_from_psr
-    if sample_points_from_mesh:
-        raise NotImplementedError("batch_mc_from_psr: sampling points from the meshes is not part of this build")
+    if sample_points_from_mesh and not psr_grid.is_cuda:
+        raise NotImplementedError("batch_mc_from_psr: sampling points from the meshes runs on the GPU only (no CPU path)")
     vs, fs, ns = mc_from_psr(psr_grid, zero_level=0)  # (one launch sequence for the batch; a grid's mesh does not depend on it)
+    scaled = []
     for i, (v, f, n) in enumerate(zip(vs, fs, ns)):
         if return_original_scale:
             box = torch.from_numpy(np.ascontiguousarray(v)).to(psr_grid.device)[None]
@@ -53,4 +64,19 @@ def batch_mc_from_psr(psr_grid, save_dir, save_prefix, batch_info=None, start_id
             v = box[0].cpu().numpy()
         stem = save_prefix if batch_info is None else batch_info[i]
         save_mesh(os.path.join(save_dir, "%s_%05d.ply" % (stem, start_idx + i)), v, f, normals=n)
-    return [], [], [], []
+        scaled.append(v)
+    if not sample_points_from_mesh:
+        return [], [], [], []
+    from slide_amd import _ext, mesh
+    dev = psr_grid.device
+
+    def up(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev).reshape(-1, 3)
+
+    meshes = [(up(v, np.float32), up(f, np.int32), up(n, np.float32)) for v, f, n in zip(scaled, fs, ns)]
+    ids = [start_idx + i for i in range(len(meshes))]
+    points, normals = mesh.sample_points_from_meshes(meshes, num_samples, return_normals=True, seed=seed, mesh_ids=ids, stream_id=0)
+    dense, dense_n = mesh.sample_points_from_meshes(meshes, num_dense, return_normals=True, seed=seed, mesh_ids=ids, stream_id=1)
+    uniform, sel = _ext.sample_farthest_points(dense, K=num_samples, start_idx=torch.zeros(len(meshes), dtype=torch.int64, device=dev))
+    uniform_n = torch.gather(dense_n, 1, sel.unsqueeze(-1).expand(-1, -1, 3))
+    return tuple(t.cpu().numpy() for t in (points, normals, uniform, uniform_n))

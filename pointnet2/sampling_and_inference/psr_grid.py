@@ -11,6 +11,12 @@ decode CLIs and the meshes (--save_mesh_dir: marching cubes on the GPU, slide_am
   --save out.npz               receives `psr_grid` (n, r, r, r), `points` (n, N, 3) as DPSR saw them (in [0, 0.99]) and `normals`
   --save_mesh_dir DIR          also one triangle mesh per shape, DIR/<prefix>_<index:05d>.ply (vertices in [0, 1), with normals)
   --mesh_prefix P              ... the prefix (default mesh)
+  --sample_points_from_mesh    (with --save_mesh_dir) also DIR/points_sampled_from_mesh.npz: `points`, `normals` (n, 2048, 3), 2048
+                               area-weighted samples of every mesh with unit face normals, and
+                               DIR/uniform_points_sampled_from_mesh.npz: 20480 samples reduced to 2048 by farthest point sampling.
+                               Shape i draws under the id i, so the files do not depend on --batch_size; score them with
+                               generation_evaluate.py --samples DIR/uniform_points_sampled_from_mesh.npz --ref <reference set>
+  --sample_seed N              ... the seed of the draw (default 0)
 """
 import argparse
 import os
@@ -35,7 +41,11 @@ def main():
     ap.add_argument("--save", type=str, required=True)
     ap.add_argument("--save_mesh_dir", type=str, default=None, help="also write one PLY mesh per shape into this directory")
     ap.add_argument("--mesh_prefix", type=str, default="mesh")
+    ap.add_argument("--sample_points_from_mesh", action="store_true", help="also sample point sets from the meshes (needs --save_mesh_dir)")
+    ap.add_argument("--sample_seed", type=int, default=0)
     a = ap.parse_args()
+    if a.sample_points_from_mesh and not a.save_mesh_dir:
+        ap.error("--sample_points_from_mesh requires --save_mesh_dir")
 
     import torch
     from dpsr_evaluation import batch_mc_from_psr, points_to_dpsr_grid
@@ -57,7 +67,7 @@ def main():
         raise SystemExit("psr_grid.py needs a GPU")
     dev = torch.device("cuda:0")
     dpsr = DPSR((a.grid_res,) * 3, sig=a.psr_sigma).to(dev)
-    grids, pts = [], []
+    grids, pts, sampled = [], [], []
     if a.save_mesh_dir:
         os.makedirs(a.save_mesh_dir, exist_ok=True)
     for s in range(0, points.shape[0], a.batch_size):
@@ -67,12 +77,20 @@ def main():
         grids.append(grid.cpu().numpy())
         pts.append(p.cpu().numpy())
         if a.save_mesh_dir:
-            batch_mc_from_psr(grid, a.save_mesh_dir, a.mesh_prefix, start_idx=s)
+            out = batch_mc_from_psr(grid, a.save_mesh_dir, a.mesh_prefix, start_idx=s, sample_points_from_mesh=a.sample_points_from_mesh,
+                                    seed=a.sample_seed)
+            if a.sample_points_from_mesh:
+                sampled.append(out)
     os.makedirs(os.path.dirname(os.path.abspath(a.save)), exist_ok=True)
     np.savez(a.save, psr_grid=np.concatenate(grids), points=np.concatenate(pts), normals=normals)
     print("psr_grid %s has been saved to %s" % (np.concatenate(grids).shape, a.save))
     if a.save_mesh_dir:
         print("%d meshes have been saved to %s" % (points.shape[0], a.save_mesh_dir))
+    if a.sample_points_from_mesh:
+        p, n, up, un = (np.concatenate([o[k] for o in sampled]) for k in range(4))
+        np.savez(os.path.join(a.save_mesh_dir, "points_sampled_from_mesh.npz"), points=p, normals=n)
+        np.savez(os.path.join(a.save_mesh_dir, "uniform_points_sampled_from_mesh.npz"), points=up, normals=un)
+        print("point sets %s sampled from the meshes have been saved to %s" % (p.shape, a.save_mesh_dir))
 
 
 if __name__ == "__main__":

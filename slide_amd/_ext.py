@@ -758,3 +758,109 @@ def marching_cubes(phi, level=0.0, chunk=None):
         for v, f, v0, f0 in tot:
             out.append((verts[v0:v0 + v], faces[f0:f0 + f], normals[v0:v0 + v]))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- mesh sampling
+MESH_SAMPLE_MAX_BATCH = 65535
+
+
+def mesh_cdf_span(level):
+    """faces per thread (0), wave (1) and workgroup pass (2) of the cdf scan (slide_mesh_cdf_span)"""
+    return lib().slide_mesh_cdf_span(int(level))
+
+
+def _mesh_offsets(off, rows, name, dev):
+    """host offsets (b + 1) -> (device int64 tensor, b): checked here, because the kernels trust them"""
+    off = [int(x) for x in (off.tolist() if hasattr(off, "tolist") else off)]
+    if len(off) < 1 or off[0] != 0 or off[-1] != rows or any(a > b for a, b in zip(off, off[1:])):
+        raise ValueError("%s must run from 0 to %d without decreasing, got %s" % (name, rows, off if len(off) <= 8 else off[:8] + ["..."]))
+    return torch.tensor(off, device=dev, dtype=torch.int64), len(off) - 1
+
+
+def _mesh_arrays(verts, faces, voff, foff):
+    verts = _chk_f32_cuda(verts, "verts", 2)
+    if not isinstance(faces, torch.Tensor) or not faces.is_cuda:
+        raise RuntimeError("faces must be a CUDA tensor")
+    _chk_int(faces, "faces")
+    faces = faces.contiguous()
+    if verts.size(1) != 3 or faces.dim() != 2 or faces.size(1) != 3:
+        raise ValueError("packed meshes are verts (sum V, 3) and faces (sum F, 3), got %s and %s" % (tuple(verts.shape), tuple(faces.shape)))
+    if faces.size(0) > 2 ** 31 - 1:
+        raise ValueError("at most 2^31 - 1 faces per call")
+    vo, b = _mesh_offsets(voff, verts.size(0), "voff", verts.device)
+    fo, bf = _mesh_offsets(foff, faces.size(0), "foff", verts.device)
+    if b != bf:
+        raise ValueError("voff and foff describe %d and %d meshes" % (b, bf))
+    return verts, faces, vo, fo, b
+
+
+def mesh_face_cdf(verts, faces, voff, foff):
+    """slide_mesh_face_cdf on packed meshes: verts (sum V, 3) f32 and faces (sum F, 3) int32 CUDA tensors (vertex indices local to the
+    mesh), voff / foff (b + 1) HOST offsets -> (areas (sum F,) f32, cdf (sum F,) int64 holding the uint64 sums, voff, foff as device
+    tensors).  ValueError after one read of the flag word for a face index out of its mesh's range or a non-finite vertex of a face."""
+    verts, faces, vo, fo, b = _mesh_arrays(verts, faces, voff, foff)
+    nf = faces.size(0)
+    areas = torch.empty(nf, device=verts.device, dtype=torch.float32)
+    cdf = torch.empty(nf, device=verts.device, dtype=torch.int64)
+    if b and nf:
+        if not verts.size(0):
+            raise ValueError("mesh_face_cdf: faces without vertices")
+        flag = torch.zeros(1, device=verts.device, dtype=torch.int32)
+        check(lib().slide_mesh_face_cdf(b, nf, ptr(verts), ptr(faces), ptr(vo), ptr(fo), ptr(areas), ptr(cdf), ptr(flag), stream_of()),
+              "mesh_face_cdf")
+        f = int(flag.item())
+        if f & 1:
+            raise ValueError("mesh_face_cdf: a face holds a vertex index outside [0, V) of its mesh")
+        if f & 2:
+            raise ValueError("mesh_face_cdf: a face refers to a vertex with a non-finite coordinate")
+    return areas, cdf, vo, fo
+
+
+def mesh_sample(verts, faces, voff, foff, cdf, num_samples, seed=0, mesh_ids=None, stream_id=0, vnormals=None, normals=None,
+                return_face_idx=False, words=None):
+    """slide_mesh_sample with cdf, voff, foff as mesh_face_cdf returned them (device tensors): -> (points (b,S,3), normals (b,S,3)
+    or None, face_idx (b,S) int32 or None, valid (b,) int32).  normals: None, "face" or "vertex" (interpolated from vnormals
+    (sum V, 3)); mesh_ids (b,) integers, default the position; words (b,S,4) integers in [0, 2^32) replace the Philox draw."""
+    verts = _chk_f32_cuda(verts, "verts", 2)
+    for t, name, dtype in ((faces, "faces", torch.int32), (voff, "voff", torch.int64), (foff, "foff", torch.int64), (cdf, "cdf", torch.int64)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+            raise RuntimeError("%s must be a contiguous CUDA %s tensor, as mesh_face_cdf returns it" % (name, dtype))
+    if voff.numel() != foff.numel() or voff.numel() < 1 or cdf.numel() != faces.size(0):
+        raise ValueError("mesh_sample: voff, foff and cdf do not describe the same meshes")
+    dev, b, S = verts.device, voff.numel() - 1, int(num_samples)
+    if normals not in (None, "face", "vertex"):
+        raise ValueError("normals must be None, 'face' or 'vertex', got %r" % (normals,))
+    if S < 0:
+        raise ValueError("num_samples must not be negative")
+    if b > MESH_SAMPLE_MAX_BATCH:
+        raise ValueError("at most %d meshes per call" % MESH_SAMPLE_MAX_BATCH)
+    if normals == "vertex":
+        if vnormals is None:
+            raise ValueError("normals='vertex' needs the meshes' vertex normals")
+        vnormals = _chk_f32_cuda(vnormals, "vertex normals", 2)
+        if vnormals.shape != verts.shape:
+            raise ValueError("vertex normals %s do not match verts %s" % (tuple(vnormals.shape), tuple(verts.shape)))
+    seed = int(seed) & (2 ** 64 - 1)
+    i32 = lambda w: ((int(w) & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000  # noqa: E731  (the C int with that bit pattern)
+    ids = None
+    if mesh_ids is not None:
+        ids = torch.as_tensor([i32(x) for x in (mesh_ids.tolist() if hasattr(mesh_ids, "tolist") else mesh_ids)], dtype=torch.int32).to(dev)
+        if ids.numel() != b:
+            raise ValueError("mesh_ids must hold one number per mesh (%d), got %d" % (b, ids.numel()))
+    if words is not None:
+        words = torch.as_tensor(words)
+        if tuple(words.shape) != (b, S, 4):
+            raise ValueError("words must be (b, S, 4) = %s, got %s" % ((b, S, 4), tuple(words.shape)))
+        # uint32 bit patterns in an int32 tensor
+        words = ((words.to(torch.int64) & 0xFFFFFFFF) ^ 0x80000000).sub_(0x80000000).to(torch.int32).to(dev).contiguous()
+    f32 = dict(device=dev, dtype=torch.float32)
+    points = torch.zeros((b, S, 3), **f32)
+    out_n = torch.zeros((b, S, 3), **f32) if normals else None
+    fidx = torch.full((b, S), -1, device=dev, dtype=torch.int32) if return_face_idx else None
+    valid = torch.zeros(b, device=dev, dtype=torch.int32)
+    if b and S and faces.size(0) and verts.size(0):
+        check(lib().slide_mesh_sample(b, S, ptr(verts), ptr(faces), ptr(vnormals) if normals == "vertex" else None, ptr(voff),
+                                      ptr(foff), ptr(cdf), i32(seed), i32(seed >> 32), i32(stream_id), ptr(ids), ptr(words),
+                                      1 if normals == "vertex" else 0, ptr(points), ptr(out_n), ptr(fidx), ptr(valid), stream_of()),
+              "mesh_sample")
+    return points, out_n, fidx, valid

@@ -188,6 +188,9 @@ PROTOTYPES = {name: _proto(args) for name, args in {
     "slide_mc_bricks": "i",
     "slide_mc_count": "iipfppp",
     "slide_mc_emit": "iipfppppppp",
+    "slide_mesh_cdf_span": "i",
+    "slide_mesh_face_cdf": "iqpppppppp",
+    "slide_mesh_sample": "ii" + "pppppp" + "iii" + "pp" + "i" + "ppppp",
     "slide_hip_device_ok": "",
     "slide_lane_reduce_selftest": "pppip",
     "slide_philox_normal_selftest": "iiiiiipp",

@@ -1,5 +1,6 @@
-"""Triangle meshes from indicator grids: marching cubes on the HIP kernels of csrc/marching_cubes.hip, and a PLY reader / writer
-in numpy (what the reference does with skimage.measure.marching_cubes and pytorch3d.io.save_ply)."""
+"""Triangle meshes from indicator grids: marching cubes on the HIP kernels of csrc/marching_cubes.hip, area-weighted point samples
+from the meshes on those of csrc/mesh_sample.hip, and a PLY reader / writer in numpy (what the reference does with
+skimage.measure.marching_cubes, pytorch3d.ops.sample_points_from_meshes and pytorch3d.io.save_ply)."""
 import numpy as np
 
 from . import _ext
@@ -80,3 +81,61 @@ def load_ply(path):
                     normals = np.stack([block[c] for c in ("nx", "ny", "nz")], axis=1).astype(np.float32)
         end += dt.itemsize * count
     return verts, faces, normals
+
+
+def pack_meshes(meshes):
+    """a list of (verts (V,3) f32, faces (F,3) int32[, normals (V,3) f32 or None]) CUDA tensors -> (verts (sum V,3), faces (sum F,3),
+    normals (sum V,3) or None when a mesh lacks them, voff, foff): one torch.cat per array, the offsets as host lists"""
+    import torch
+    if len(meshes) == 0:
+        raise ValueError("pack_meshes: an empty list of meshes has no device")
+    for m in meshes:
+        for t, what in zip(m[:3], ("verts", "faces", "normals")):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise RuntimeError("sample_points_from_meshes runs on the GPU only: %s must be a CUDA tensor" % what)
+            if torch.is_grad_enabled() and t.requires_grad:
+                raise NotImplementedError("sample_points_from_meshes is forward only (no backward kernels): call it under "
+                                          "torch.no_grad() or on tensors that do not require grad")
+        if m[0].dim() != 2 or m[0].size(1) != 3 or m[1].dim() != 2 or m[1].size(1) != 3:
+            raise ValueError("a mesh is verts (V, 3) and faces (F, 3), got %s and %s" % (tuple(m[0].shape), tuple(m[1].shape)))
+    voff, foff = [0], [0]
+    for m in meshes:
+        voff.append(voff[-1] + m[0].size(0))
+        foff.append(foff[-1] + m[1].size(0))
+    verts = torch.cat([m[0].detach() for m in meshes])
+    faces = torch.cat([m[1].detach() for m in meshes])
+    normals = None
+    if all(len(m) > 2 and m[2] is not None for m in meshes):
+        normals = torch.cat([m[2].detach() for m in meshes])
+    return verts, faces, normals, voff, foff
+
+
+def sample_points_from_meshes(meshes, num_samples=10000, return_normals=False, seed=0, mesh_ids=None, stream_id=0, normals="face",
+                              return_face_idx=False, words=None):
+    """pytorch3d.ops.sample_points_from_meshes on the HIP kernels of csrc/mesh_sample.hip, for the whole batch in three launches.
+    meshes: the list of (verts, faces, normals) that marching_cubes returns, or hand-made CUDA tensors (f32, int32, f32 or absent).
+    -> points (B, S, 3) [, normals (B, S, 3)] [, face_idx (B, S) int32, the face's row in its mesh].
+
+    A face is drawn with probability proportional to its area, quantised to 32 bits below the mesh's largest area, by ONE
+    Philox4x32-10 call per sample keyed with `seed` on the counter (sample, mesh id, stream_id, constant); the point has pytorch3d's
+    barycentric weights (1 - sqrt u, sqrt u (1 - v), sqrt u v).  mesh_ids (default: the position in the list) names a mesh's noise: a
+    mesh's samples depend on (mesh, seed, mesh id, stream_id) alone, not on the batch or the position; two runs are bit-equal.
+    normals: "face" = the unit face normal (v1 - v0) x (v2 - v0), what pytorch3d returns; "vertex" = the vertex normals interpolated
+    with the weights and normalised.  A mesh without faces or of zero area yields zeros (pytorch3d's behaviour).  words (B, S, 4)
+    integers in [0, 2^32) replace the Philox draw.  ValueError for a face index out of range or a non-finite vertex of a face.
+    CUDA only, no autograd."""
+    if normals not in ("face", "vertex"):
+        raise ValueError("normals must be 'face' or 'vertex', got %r" % (normals,))
+    verts, faces, vnormals, voff, foff = pack_meshes(meshes)
+    if normals == "vertex" and vnormals is None:
+        raise ValueError("normals='vertex' needs vertex normals for every mesh")
+    verts, faces = verts.float(), faces.int()  # (no copies of float32 / int32 tensors)
+    _, cdf, vo, fo = _ext.mesh_face_cdf(verts, faces, voff, foff)
+    points, out_n, fidx, _ = _ext.mesh_sample(verts, faces, vo, fo, cdf, num_samples, seed=seed, mesh_ids=mesh_ids,
+                                              stream_id=stream_id, vnormals=vnormals if normals == "vertex" else None,
+                                              normals=normals if return_normals else None, return_face_idx=return_face_idx,
+                                              words=words)
+    out = (points,) + ((out_n,) if return_normals else ()) + ((fidx,) if return_face_idx else ())
+    return out[0] if len(out) == 1 else out
