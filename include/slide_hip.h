@@ -24,6 +24,9 @@
  * Part 6 is marching cubes, the indicator grid to an indexed triangle mesh (the reference calls skimage.measure.marching_cubes on the
  * host: pointnet2/dpsr_utils/utils.py mc_from_psr).
  *
+ * Part 8 is mesh clean-up: connected components of a batch of triangle meshes and the keep-largest filter (the reference's
+ * verts_on_largest_mesh in the same file, igl and trimesh on the host).
+ *
  * Part 3 is the fused latent-DDPM denoiser engine (the reference runs these as ~80 torch module
  * launches per step: pointnet2/models/pointnet2_with_pcld_condition.py:286-489).
  */
@@ -278,6 +281,66 @@ SLIDE_API int slide_mesh_sample(int b, int s, const float *verts, const int *fac
                                 const long long *foff, const unsigned long long *cdf, int seed_lo, int seed_hi, int stream_id,
                                 const int *mesh_ids, const unsigned *words, int vertex_normals, float *points, float *normals,
                                 int *face_idx, int *valid, slide_stream_t stream);
+
+/* ------------------------------------------------------------------ Part 8: connected components of triangle meshes, keep-largest filter */
+/* Mesh clean-up (the reference's verts_on_largest_mesh, pointnet2/dpsr_utils/utils.py: igl connected_components and trimesh split on
+ * the host, one mesh at a time) for a PACKED batch as in Part 7.  Integers only; vertex coordinates play no part in labelling.
+ *
+ *   graph       the nodes are the mesh's V vertices; any two DISTINCT indices of one face are joined.  (a, a, b) gives the edge a-b,
+ *               (a, a, a) none (it still belongs to a's component).  A vertex no face refers to is a component of its own.
+ *   root[v]     the smallest vertex index of v's component: a function of the mesh alone.
+ *   cid[v]      the rank of root[v] among the mesh's roots in ascending order, 0 .. C-1 (scipy's and igl's numbering).
+ *   counts      nverts[c]; nfaces[c] = the faces whose FIRST index lies in c.
+ *   selection   candidates are the components with nfaces >= 1 whose size (by = 0: nverts, 1: nfaces) is >= min_size.  keep_all = 0
+ *               keeps the largest candidate, ties to the lowest cid (numpy argmax); keep_all != 0 keeps every candidate.  No
+ *               candidate: the mesh comes out empty.
+ *   compaction  kept vertices and kept faces (those whose first vertex is kept) keep their relative order and winding; vertex and
+ *               normal rows are copied bit for bit; face indices are renumbered.  Every output vertex has an output face.
+ *   refusal     a face index outside [0, V) of its mesh is tested BEFORE it is used as an address: the face joins nothing and
+ *               info[0] = 1 (slide_mesh_cc_label); later stages skip such a face.
+ *
+ * Labelling: L[v] = v; a ROUND is two launches: hook (a thread per face: m = the minimum of the three labels and of THEIR labels,
+ * integer atomicMin of m into the three vertices and into their labels) and jump (a thread per vertex: L[v] = L[L[..L[v]]], at most
+ * 8 steps).  Labels only decrease, stay inside the component and are bounded below by its root, so a stale read within a launch is
+ * an older upper bound: it can cost a round, never the result.  A round that lowers nothing was read entirely fresh, and then every
+ * face has equal labels and L[L[v]] = L[v]: L is constant on a component, and since L[root] = root that constant is the root.  The
+ * fixed point is unique, so the labels do not depend on the execution order, the batch or the position.
+ * Cap: launches are ordered, so at a round's start every label a previous round wrote is visible.  By induction a vertex at graph
+ * distance d from its root holds the root after round d (its neighbour at distance d - 1 held it at the round's start, and their
+ * common face writes it); round d + 1 then changes nothing.  max_rounds = (largest V of the batch) + 1 therefore always suffices;
+ * meshes from marching cubes need about log2 V rounds.  More rounds than max_rounds return -5 (never an unbounded loop).
+ * The host reads two words (refusal, last round that lowered a label) once per `group` rounds and synchronises the stream for it:
+ * slide_mesh_cc_label is the one entry point here that BLOCKS.  Surplus rounds at the fixed point change nothing.
+ * No float atomics, no spin-waiting, no inter-workgroup barrier: every launch is one grid over the packed faces or vertices.
+ *
+ * Limits: sum V and sum F <= 2^31 - 1, b <= 65535.  All four entry points return -2 for a count out of range or a NULL array before
+ * any launch and 0 without a launch for b = 0 or sum V = 0.
+ *
+ * Spans, in elements: level 0 one workgroup of the per-face / per-vertex launches, 1 one wave of a scan, 2 one pass of a mesh's
+ * workgroup in a scan; -2 otherwise. */
+SLIDE_API int slide_mesh_cc_span(int level);
+/* labels (sum V) int32 receives root[v] (LOCAL index).  state (2) int32 is device scratch.  info (4) int32 on the HOST receives
+ * {refusal flag, rounds that lowered a label, host reads, rounds issued}.  group >= 1 rounds per host read, max_rounds >= 1. */
+SLIDE_API int slide_mesh_cc_label(int b, long long nv, long long nf, const int *faces, const long long *voff, const long long *foff,
+                                  int *labels, int *state, int group, int max_rounds, int *info, slide_stream_t stream);
+/* With labels as slide_mesh_cc_label left them: cnt_v, cnt_f (sum V) int32 = vertices / faces per component AT ITS ROOT's row (int32
+ * atomic adds: exact, order-free), rank (sum V) int32 = the cid at every root's row (other rows are not written), cid (sum V) int32,
+ * nverts / nfaces (sum V) int32 whose first C rows of every mesh (from voff[m]) hold the counts by cid, totals (b, 4) int32 whose
+ * column 2 receives C.  Two memsets and two launches: counts, then one workgroup per mesh (scan of the root flags in passes). */
+SLIDE_API int slide_mesh_cc_stats(int b, long long nv, long long nf, const int *faces, const long long *voff, const long long *foff,
+                                  const int *labels, int *cnt_v, int *cnt_f, int *rank, int *cid, int *nverts, int *nfaces, int *totals,
+                                  slide_stream_t stream);
+/* Selection and the two exclusive scans, one workgroup per mesh: vnew (sum V) / fnew (sum F) int32 = the row's place among the kept
+ * rows of its mesh, or -1; totals columns 0, 1, 3 receive V', F' and the selected root (-1: none, or keep_all). */
+SLIDE_API int slide_mesh_cc_select(int b, long long nv, long long nf, const int *faces, const long long *voff, const long long *foff,
+                                   const int *labels, const int *cnt_v, const int *cnt_f, int by, long long min_size, int keep_all,
+                                   int *vnew, int *fnew, int *totals, slide_stream_t stream);
+/* One launch over the packed vertices and faces: out_verts (sum V', 3), out_normals (or NULL with normals NULL), vert_idx (sum V')
+ * int32 = the row's index in its input mesh, out_faces (sum F', 3) int32.  ovoff / ofoff (b + 1) int64: the prefix sums of V' / F'. */
+SLIDE_API int slide_mesh_cc_compact(int b, long long nv, long long nf, const float *verts, const float *normals, const int *faces,
+                                    const long long *voff, const long long *foff, const int *vnew, const int *fnew,
+                                    const long long *ovoff, const long long *ofoff, float *out_verts, float *out_normals,
+                                    int *out_faces, int *vert_idx, slide_stream_t stream);
 
 /* ------------------------------------------------------------------ Part 3: denoiser engine */
 /* see slide_engine.h */

@@ -1,6 +1,7 @@
 """Point clouds -> DPSR indicator grids: the coordinate transformations of the reference's pointnet2/dpsr_evaluation.py
 (shapenet_psr_normalize lines 22-32, compute_center_and_max_length 34-43, the tail of network_output_to_dpsr_grid 77-86), and DPSR
-grids -> meshes on disk and the point sets sampled from them (batch_mc_from_psr 291-340).  The refine-and-upsample network in front of
+grids -> meshes on disk, optionally reduced to their largest connected component, and the point sets sampled from them
+(batch_mc_from_psr 291-340).  The refine-and-upsample network in front of
 them and the evaluation loop behind them are not part of this build."""
 import os
 
@@ -36,7 +37,7 @@ def points_to_dpsr_grid(points, normals, dpsr, scale=1, explicit_normalize=False
 
 def batch_mc_from_psr(psr_grid, save_dir, save_prefix, batch_info=None, start_idx=0, sample_points_from_mesh=False,
                       return_original_scale=False, original_center=None, original_max_length=None, seed=0, num_samples=2048,
-                      num_dense=20480):
+                      num_dense=20480, largest_component=False):
     """marching cubes of psr_grid (B, res, res, res) and one PLY per shape: <save_prefix>_<start_idx + i:05d>.ply under save_dir (or
     <batch_info[i]>_<...>.ply).  The vertices are in [0, 1) (divided by res); with return_original_scale the mesh's bounding box is
     mapped to original_center (B, 1, 3) and original_max_length (B, 1, 1).  Returns the reference's four results; they are empty
@@ -49,12 +50,26 @@ def batch_mc_from_psr(psr_grid, save_dir, save_prefix, batch_info=None, start_id
 
     One sampling call serves the batch.  Mesh i draws with the id start_idx + i under `seed`: a shape's samples do not depend on
     how the shapes are split into batches.  (The reference samples with torch's global generator, one mesh at a time, and starts
-    the farthest point sampling at a random index.)"""
+    the farthest point sampling at a random index.)
+
+    largest_component: every mesh is reduced to its connected component with the most vertices (slide_amd.mesh.filter_components, one
+    call for the batch; the reference's verts_on_largest_mesh) directly after extraction: the bounding box of return_original_scale,
+    the PLY and the samples are the kept component's.  Mesh ids and seeds are unchanged."""
     from dpsr_utils.io_utils import save_mesh
     from dpsr_utils.utils import mc_from_psr
     if sample_points_from_mesh and not psr_grid.is_cuda:
         raise NotImplementedError("batch_mc_from_psr: sampling points from the meshes runs on the GPU only (no CPU path)")
     vs, fs, ns = mc_from_psr(psr_grid, zero_level=0)  # (one launch sequence for the batch; a grid's mesh does not depend on it)
+    dev = psr_grid.device
+
+    def up(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev).reshape(-1, 3)
+
+    if largest_component:
+        from slide_amd import mesh
+        kept = mesh.filter_components([(up(v, np.float32), up(f, np.int32), up(n, np.float32)) for v, f, n in zip(vs, fs, ns)],
+                                      keep="largest", by="verts")
+        vs, fs, ns = ([k[j].cpu().numpy() for k in kept] for j in range(3))
     scaled = []
     for i, (v, f, n) in enumerate(zip(vs, fs, ns)):
         if return_original_scale:
@@ -68,11 +83,6 @@ def batch_mc_from_psr(psr_grid, save_dir, save_prefix, batch_info=None, start_id
     if not sample_points_from_mesh:
         return [], [], [], []
     from slide_amd import _ext, mesh
-    dev = psr_grid.device
-
-    def up(a, dtype):
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev).reshape(-1, 3)
-
     meshes = [(up(v, np.float32), up(f, np.int32), up(n, np.float32)) for v, f, n in zip(scaled, fs, ns)]
     ids = [start_idx + i for i in range(len(meshes))]
     points, normals = mesh.sample_points_from_meshes(meshes, num_samples, return_normals=True, seed=seed, mesh_ids=ids, stream_id=0)

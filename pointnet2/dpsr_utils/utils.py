@@ -10,6 +10,7 @@ and its mesh helpers (lines 246-287, 498-507) on slide_amd/mesh.py:
 
   mc_from_psr(psr_grid, ...)       marching cubes of every grid of a batch on the GPU, (verts, faces, normals) lists of length B
   export_mesh(name, v, f)          a binary PLY of one mesh
+  verts_on_largest_mesh(v, f)      the connected component with the most vertices (lines 352-375: igl + trimesh on the host there)
 """
 import numpy as np
 import torch
@@ -78,3 +79,21 @@ def export_mesh(name, v, f):
     if len(v.shape) > 2:
         v, f = v[0], f[0]
     mesh.save_ply(name, v, f)
+
+
+def verts_on_largest_mesh(verts, faces):
+    """verts (N, 3) and faces (F, 3), numpy arrays or tensors (squeezed like the reference's) -> (v_large (N', 3) float32, f_large
+    (F', 3) int32) as numpy arrays: the connected component with the most vertices (ties: the one holding the smallest vertex index,
+    the reference's argmax), vertices and faces in their order, faces renumbered.  Runs on the GPU (slide_amd.mesh.filter_components):
+    host inputs are uploaded; there is no CPU path."""
+    from slide_amd import mesh
+
+    def dev(a, dtype):
+        if torch.is_tensor(a):
+            a = a.detach().squeeze()
+        else:
+            a = torch.from_numpy(np.ascontiguousarray(np.squeeze(np.asarray(a))))
+        return a.to(device="cuda", dtype=dtype).reshape(-1, 3).contiguous()
+
+    (v, f, _), = mesh.filter_components([(dev(verts, torch.float32), dev(faces, torch.int32))], keep="largest", by="verts")
+    return v.cpu().numpy(), f.cpu().numpy()

@@ -17,6 +17,9 @@ decode CLIs and the meshes (--save_mesh_dir: marching cubes on the GPU, slide_am
                                Shape i draws under the id i, so the files do not depend on --batch_size; score them with
                                generation_evaluate.py --samples DIR/uniform_points_sampled_from_mesh.npz --ref <reference set>
   --sample_seed N              ... the seed of the draw (default 0)
+  --largest_component          (with --save_mesh_dir) keep only every mesh's connected component with the most vertices (on the GPU,
+                               slide_amd/mesh.py filter_components) before it is written and sampled: small blobs away from the
+                               shape are dropped.  Without the flag every file is what it was
 """
 import argparse
 import os
@@ -43,9 +46,12 @@ def main():
     ap.add_argument("--mesh_prefix", type=str, default="mesh")
     ap.add_argument("--sample_points_from_mesh", action="store_true", help="also sample point sets from the meshes (needs --save_mesh_dir)")
     ap.add_argument("--sample_seed", type=int, default=0)
+    ap.add_argument("--largest_component", action="store_true", help="keep only every mesh's largest connected component (needs --save_mesh_dir)")
     a = ap.parse_args()
     if a.sample_points_from_mesh and not a.save_mesh_dir:
         ap.error("--sample_points_from_mesh requires --save_mesh_dir")
+    if a.largest_component and not a.save_mesh_dir:
+        ap.error("--largest_component requires --save_mesh_dir")
 
     import torch
     from dpsr_evaluation import batch_mc_from_psr, points_to_dpsr_grid
@@ -78,7 +84,7 @@ def main():
         pts.append(p.cpu().numpy())
         if a.save_mesh_dir:
             out = batch_mc_from_psr(grid, a.save_mesh_dir, a.mesh_prefix, start_idx=s, sample_points_from_mesh=a.sample_points_from_mesh,
-                                    seed=a.sample_seed)
+                                    seed=a.sample_seed, largest_component=a.largest_component)
             if a.sample_points_from_mesh:
                 sampled.append(out)
     os.makedirs(os.path.dirname(os.path.abspath(a.save)), exist_ok=True)

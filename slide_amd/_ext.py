@@ -8,6 +8,8 @@ hand-written gfx950 HIP kernels through the C-ABI in include/slide_hip.h.
 Asynchronous on torch's current stream, no host sync, inputs borrowed and never mutated.
 """
 
+import ctypes
+
 import torch
 
 from ._lib import check, lib
@@ -864,3 +866,113 @@ def mesh_sample(verts, faces, voff, foff, cdf, num_samples, seed=0, mesh_ids=Non
                                       1 if normals == "vertex" else 0, ptr(points), ptr(out_n), ptr(fidx), ptr(valid), stream_of()),
               "mesh_sample")
     return points, out_n, fidx, valid
+
+
+# ---------------------------------------------------------------------------------------------------------------- mesh components
+MESH_CC_GROUP = 4  # rounds of labelling per host read of the status words (profiles/mesh_components.md)
+_MESH_CC_ROUND_CAP = -5  # slide_mesh_cc_label: more rounds than max_rounds
+
+
+def mesh_cc_span(level):
+    """elements per workgroup of the per-face / per-vertex launches (0), per wave (1) and per workgroup pass (2) of the per-mesh scans
+    (slide_mesh_cc_span)"""
+    return lib().slide_mesh_cc_span(int(level))
+
+
+def mesh_cc_label(faces, voff, foff, nv, group=None, max_rounds=None):
+    """slide_mesh_cc_label on packed faces (sum F, 3) int32 CUDA (vertex indices local to the mesh) with HOST offsets voff / foff (b + 1)
+    and nv = sum V -> (labels (sum V,) int32 = every vertex's root, the smallest index of its component; voff, foff as device tensors;
+    info = dict(rounds, reads, issued)).  ValueError for a face index outside [0, V) of its mesh (tested on the device before it is
+    used; the status words are read once per `group` rounds); RuntimeError beyond max_rounds (default: the largest V + 1, which
+    always suffices)."""
+    if not isinstance(faces, torch.Tensor) or not faces.is_cuda:
+        raise RuntimeError("faces must be a CUDA tensor")
+    _chk_int(faces, "faces")
+    faces = faces.contiguous()
+    if faces.dim() != 2 or faces.size(1) != 3:
+        raise ValueError("packed faces are (sum F, 3), got %s" % (tuple(faces.shape),))
+    nv, nf, dev = int(nv), faces.size(0), faces.device
+    if nv > 2 ** 31 - 1 or nf > 2 ** 31 - 1:
+        raise ValueError("at most 2^31 - 1 vertices and faces per call")
+    vo, b = _mesh_offsets(voff, nv, "voff", dev)
+    fo, bf = _mesh_offsets(foff, nf, "foff", dev)
+    if b != bf:
+        raise ValueError("voff and foff describe %d and %d meshes" % (b, bf))
+    if b > MESH_SAMPLE_MAX_BATCH:
+        raise ValueError("at most %d meshes per call" % MESH_SAMPLE_MAX_BATCH)
+    if nf and not nv:
+        raise ValueError("mesh_components: faces without vertices")
+    host_v = [int(x) for x in (voff.tolist() if hasattr(voff, "tolist") else voff)]
+    group = MESH_CC_GROUP if group is None else int(group)
+    cap = (max(hi - lo for lo, hi in zip(host_v, host_v[1:])) + 1 if b else 1) if max_rounds is None else int(max_rounds)
+    if group < 1 or cap < 1:
+        raise ValueError("group and max_rounds must be positive")
+    labels = torch.empty(nv, device=dev, dtype=torch.int32)
+    info = (ctypes.c_int * 4)()
+    if b and nv:
+        state = torch.empty(2, device=dev, dtype=torch.int32)
+        st = lib().slide_mesh_cc_label(b, nv, nf, ptr(faces), ptr(vo), ptr(fo), ptr(labels), ptr(state), group, cap,
+                                       ctypes.addressof(info), stream_of())
+        if st == _MESH_CC_ROUND_CAP:
+            raise RuntimeError("mesh_components: the labels did not settle within %d rounds" % cap)
+        check(st, "mesh_cc_label")
+        if info[0]:
+            raise ValueError("mesh_components: a face holds a vertex index outside [0, V) of its mesh")
+    return labels, vo, fo, dict(rounds=int(info[1]), reads=int(info[2]), issued=int(info[3]))
+
+
+def mesh_cc_stats(faces, voff, foff, labels):
+    """slide_mesh_cc_stats with labels, voff, foff as mesh_cc_label returned them -> (cid (sum V,), nverts (sum V,), nfaces (sum V,),
+    totals (b, 4), cnt_v, cnt_f): int32 device tensors; nverts / nfaces hold a mesh's C counts from its first row on, totals[:, 2] = C;
+    cnt_v / cnt_f hold the counts at every root's row (what mesh_cc_select reads)."""
+    nv, nf, b, dev = labels.numel(), faces.size(0), voff.numel() - 1, labels.device
+    new = lambda n: torch.empty(n, device=dev, dtype=torch.int32)  # noqa: E731
+    cnt_v, cnt_f, rank, cid, nverts, nfaces = (new(nv) for _ in range(6))
+    totals = torch.zeros((b, 4), device=dev, dtype=torch.int32)
+    if b and nv:
+        check(lib().slide_mesh_cc_stats(b, nv, nf, ptr(faces), ptr(voff), ptr(foff), ptr(labels), ptr(cnt_v), ptr(cnt_f), ptr(rank),
+                                        ptr(cid), ptr(nverts), ptr(nfaces), ptr(totals), stream_of()), "mesh_cc_stats")
+    return cid, nverts, nfaces, totals, cnt_v, cnt_f
+
+
+def mesh_cc_select(faces, voff, foff, labels, cnt_v, cnt_f, totals, by="verts", min_size=0, keep="largest"):
+    """slide_mesh_cc_select -> (vnew (sum V,), fnew (sum F,)) int32: a row's place among its mesh's kept rows, or -1; totals[:, 0],
+    [:, 1] and [:, 3] receive V', F' and the selected root"""
+    if by not in ("verts", "faces"):
+        raise ValueError("by must be 'verts' or 'faces', got %r" % (by,))
+    if keep not in ("largest", "all"):
+        raise ValueError("keep must be 'largest' or 'all', got %r" % (keep,))
+    nv, nf, b, dev = labels.numel(), faces.size(0), voff.numel() - 1, labels.device
+    vnew = torch.empty(nv, device=dev, dtype=torch.int32)
+    fnew = torch.full((nf,), -1, device=dev, dtype=torch.int32)
+    if b and nv:
+        check(lib().slide_mesh_cc_select(b, nv, nf, ptr(faces), ptr(voff), ptr(foff), ptr(labels), ptr(cnt_v), ptr(cnt_f),
+                                         1 if by == "faces" else 0, max(-2 ** 62, min(2 ** 62, int(min_size))), 1 if keep == "all" else 0,
+                                         ptr(vnew), ptr(fnew), ptr(totals), stream_of()), "mesh_cc_select")
+    return vnew, fnew
+
+
+def mesh_cc_compact(verts, normals, faces, voff, foff, vnew, fnew, kept_v, kept_f):
+    """slide_mesh_cc_compact with kept_v / kept_f = the HOST lists of V' / F' per mesh -> (verts (sum V', 3), normals or None,
+    faces (sum F', 3), vert_idx (sum V',), ovoff, ofoff as host lists)"""
+    verts = _chk_f32_cuda(verts, "verts", 2)
+    dev, b = verts.device, voff.numel() - 1
+    ovoff, ofoff = [0], [0]
+    for v, f in zip(kept_v, kept_f):
+        ovoff.append(ovoff[-1] + int(v))
+        ofoff.append(ofoff[-1] + int(f))
+    if normals is not None:
+        normals = _chk_f32_cuda(normals, "normals", 2)
+        if normals.shape != verts.shape:
+            raise ValueError("normals %s do not match verts %s" % (tuple(normals.shape), tuple(verts.shape)))
+    out_v = torch.empty((ovoff[-1], 3), device=dev, dtype=torch.float32)
+    out_n = torch.empty((ovoff[-1], 3), device=dev, dtype=torch.float32) if normals is not None else None
+    out_f = torch.empty((ofoff[-1], 3), device=dev, dtype=torch.int32)
+    vidx = torch.empty(ovoff[-1], device=dev, dtype=torch.int32)
+    if b and ovoff[-1]:
+        ov = torch.tensor(ovoff, device=dev, dtype=torch.int64)
+        of = torch.tensor(ofoff, device=dev, dtype=torch.int64)
+        check(lib().slide_mesh_cc_compact(b, verts.size(0), faces.size(0), ptr(verts), ptr(normals), ptr(faces), ptr(voff), ptr(foff),
+                                          ptr(vnew), ptr(fnew), ptr(ov), ptr(of), ptr(out_v), ptr(out_n), ptr(out_f), ptr(vidx),
+                                          stream_of()), "mesh_cc_compact")
+    return out_v, out_n, out_f, vidx, ovoff, ofoff

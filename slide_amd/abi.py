@@ -191,6 +191,11 @@ PROTOTYPES = {name: _proto(args) for name, args in {
     "slide_mesh_cdf_span": "i",
     "slide_mesh_face_cdf": "iqpppppppp",
     "slide_mesh_sample": "ii" + "pppppp" + "iii" + "pp" + "i" + "ppppp",
+    "slide_mesh_cc_span": "i",
+    "slide_mesh_cc_label": "iqq" + "ppppp" + "ii" + "pp",
+    "slide_mesh_cc_stats": "iqqppp" + "pppppppp" + "p",
+    "slide_mesh_cc_select": "iqqppp" + "ppp" + "iqi" + "ppp" + "p",
+    "slide_mesh_cc_compact": "iqq" + "ppp" + "pp" + "pp" + "pp" + "pppp" + "p",
     "slide_hip_device_ok": "",
     "slide_lane_reduce_selftest": "pppip",
     "slide_philox_normal_selftest": "iiiiiipp",

@@ -1,6 +1,7 @@
 """Triangle meshes from indicator grids: marching cubes on the HIP kernels of csrc/marching_cubes.hip, area-weighted point samples
-from the meshes on those of csrc/mesh_sample.hip, and a PLY reader / writer in numpy (what the reference does with
-skimage.measure.marching_cubes, pytorch3d.ops.sample_points_from_meshes and pytorch3d.io.save_ply)."""
+from the meshes on those of csrc/mesh_sample.hip, connected components and the keep-largest filter on those of
+csrc/mesh_components.hip, and a PLY reader / writer in numpy (what the reference does with skimage.measure.marching_cubes,
+pytorch3d.ops.sample_points_from_meshes, igl.connected_components + trimesh split and pytorch3d.io.save_ply)."""
 import numpy as np
 
 from . import _ext
@@ -139,3 +140,53 @@ def sample_points_from_meshes(meshes, num_samples=10000, return_normals=False, s
                                               words=words)
     out = (points,) + ((out_n,) if return_normals else ()) + ((fidx,) if return_face_idx else ())
     return out[0] if len(out) == 1 else out
+
+
+def _label(meshes):
+    verts, faces, normals, voff, foff = pack_meshes(meshes)
+    faces = faces.int()
+    labels, vo, fo, info = _ext.mesh_cc_label(faces, voff, foff, verts.size(0))
+    return verts, faces, normals, voff, foff, vo, fo, labels, info
+
+
+def mesh_components(meshes, return_info=False):
+    """connected components of every mesh of a batch on the HIP kernels of csrc/mesh_components.hip.  meshes: the list that
+    marching_cubes returns, or hand-made CUDA tensors (verts (V,3), faces (F,3) int32[, normals]).  -> per mesh a tuple
+    (labels (V,) int32, nverts (C,) int32, nfaces (C,) int32) of CUDA tensors.
+
+    Any two distinct indices of a face are joined; a vertex without a face is a component of its own.  labels[v] is the rank of the
+    smallest vertex index of v's component among those of all components (scipy.sparse.csgraph.connected_components' and igl's
+    numbering); nfaces counts a face in the component of its FIRST index.  The result is a function of the mesh alone: the same in
+    any batch, at any position, on every run.  ValueError for a face index outside [0, V).  CUDA only, no autograd.
+    return_info: also a dict with the labelling rounds that changed a label, the host reads and the rounds issued."""
+    verts, faces, _, voff, foff, vo, fo, labels, info = _label(meshes)
+    cid, nverts, nfaces, totals, _, _ = _ext.mesh_cc_stats(faces, vo, fo, labels)
+    ncomp = totals[:, 2].cpu().tolist()
+    out = [(cid[voff[m]:voff[m + 1]], nverts[voff[m]:voff[m] + c], nfaces[voff[m]:voff[m] + c]) for m, c in enumerate(ncomp)]
+    return (out, info) if return_info else out
+
+
+def filter_components(meshes, keep="largest", by="verts", min_size=0, return_index=False):
+    """keeps whole connected components of every mesh (the reference's verts_on_largest_mesh for a batch, on the GPU): -> a list of
+    (verts (V',3), faces (F',3) int32, normals (V',3) or None[, vert_idx (V',) int32]), the structure marching_cubes returns.
+
+    Candidates are the components with at least one face whose size -- by="verts": vertices, "faces": faces -- is >= min_size;
+    keep="largest" keeps the largest candidate (ties: the one holding the smallest vertex index), keep="all" every candidate.  No
+    candidate: (0,3) verts and (0,3) faces.  Kept vertices and faces keep their order and winding, rows are copied bit for bit and
+    face indices renumbered; vert_idx holds the kept rows' original indices, ascending.  Independent of the batch and reproducible,
+    like mesh_components.  ValueError for a face index outside [0, V).  CUDA only, no autograd."""
+    if keep not in ("largest", "all"):
+        raise ValueError("keep must be 'largest' or 'all', got %r" % (keep,))
+    if by not in ("verts", "faces"):
+        raise ValueError("by must be 'verts' or 'faces', got %r" % (by,))
+    verts, faces, normals, voff, foff, vo, fo, labels, _ = _label(meshes)
+    verts = verts.float()
+    _, _, _, totals, cnt_v, cnt_f = _ext.mesh_cc_stats(faces, vo, fo, labels)
+    vnew, fnew = _ext.mesh_cc_select(faces, vo, fo, labels, cnt_v, cnt_f, totals, by=by, min_size=min_size, keep=keep)
+    tot = totals.cpu().tolist()  # (the one host read that sizes the outputs)
+    out_v, out_n, out_f, vidx, ov, of = _ext.mesh_cc_compact(verts, normals, faces, vo, fo, vnew, fnew, [t[0] for t in tot], [t[1] for t in tot])
+    out = []
+    for m in range(len(tot)):
+        one = (out_v[ov[m]:ov[m + 1]], out_f[of[m]:of[m + 1]], out_n[ov[m]:ov[m + 1]] if out_n is not None else None)
+        out.append(one + (vidx[ov[m]:ov[m + 1]],) if return_index else one)
+    return out
