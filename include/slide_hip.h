@@ -27,6 +27,10 @@
  * Part 8 is mesh clean-up: connected components of a batch of triangle meshes and the keep-largest filter (the reference's
  * verts_on_largest_mesh in the same file, igl and trimesh on the host).
  *
+ * Part 9 is the refine-and-upsample front of DPSR: mirror and tag a cloud, split every point into its children, normalise and clamp
+ * them into DPSR's cube (the reference's data_utils/mirror_partial.py, models/point_upsample_module.py and the tail of
+ * network_output_to_dpsr_grid), bit for bit.
+ *
  * Part 3 is the fused latent-DDPM denoiser engine (the reference runs these as ~80 torch module
  * launches per step: pointnet2/models/pointnet2_with_pcld_condition.py:286-489).
  */
@@ -341,6 +345,52 @@ SLIDE_API int slide_mesh_cc_compact(int b, long long nv, long long nf, const flo
                                     const long long *voff, const long long *foff, const int *vnew, const int *fnew,
                                     const long long *ovoff, const long long *ofoff, float *out_verts, float *out_normals,
                                     int *out_faces, int *vert_idx, slide_stream_t stream);
+
+/* ------------------------------------------------------------------ Part 9: refine-and-upsample front of DPSR */
+/* What the reference does around its refinement network before DPSR sees a cloud (pointnet2/data_utils/mirror_partial.py,
+ * models/point_upsample_module.py, the tail of network_output_to_dpsr_grid in dpsr_evaluation.py).  All arithmetic is fp32, every
+ * product, sum and quotient rounded once in the order written (the file is compiled with contraction off; `/` is the correctly
+ * rounded division), so the outputs equal the reference's bit for bit.  No float atomics; no launch reads what another workgroup of
+ * the same launch wrote; the results of a sample do not depend on the batch, its position or the run.
+ *
+ * Both entry points own a flag (2) int32 on the device: they reset it themselves, flag[0] collects the bits named below and flag[1]
+ * the largest (sample + 1) that set one.  The caller reads it once.
+ * Status: -2 a negative count, b > 65535, a NULL array or a misaligned disp; -3 ldx not 6 or 7; -4 a disp width dw that does not match
+ * the form; -5 include_center without first_refine; -6 factor < 1.  0 without a launch for an empty batch.
+ *
+ * slide_mirror_concat: x (b, n, c) f32, c >= 3, axis in {0, 1, 2}.
+ *   center[s, k] = (float)(sum_i (double)x[s, i, k] / (double)n), the sum in a fixed order (a thread's rows ascending, then a tree
+ *                  over the workgroup's threads);  center (b, 3) is an output.
+ *   mirrored row  for k < 3:  m = x[k] - center[k];  m = -m on k == axis;  m = m + center[k]  (the centre is added back on the two
+ *                 untouched axes too, as the reference does: that can move them by an ulp).  Channel axis + 3 is negated when
+ *                 c >= 6; other channels are copied.
+ *   out (b, 2n, c + attach_label): row j is row perm[j] (or j with perm NULL) of [the n original rows, label +1; the n mirrored rows,
+ *                 label -1].  perm (2n) int32 is shared by the batch.  An entry outside [0, 2n) is tested BEFORE it is used: the row
+ *                 is filled with zeros and flag[0] |= 1.
+ *   Two launches: the centres (one workgroup per sample), then a thread per output row. */
+SLIDE_API int slide_mirror_concat(int b, int n, int c, const float *x, int axis, int attach_label, const int *perm, float *out,
+                                  float *center, int *flag, slide_stream_t stream);
+/* slide_refine_to_dpsr: X (b, m, ldx) f32 whose first 6 channels are xyz + normal (ldx 7: an indicator behind them, not read), disp
+ * (b, m, dw) f32, 8-byte aligned; the first `rows` <= m rows of every sample are split (only_original_points_split: rows = m / 2).
+ *   g = (float)(1 / sqrt((double)factor)), s = out_scale, kp = children per point, R = output rows per sample:
+ *   plain form                       dw = 6 factor        kp = factor      child[n, j, c] = X[n, c] + (disp[n, 6 j + c] * g) * s
+ *   first_refine                     dw = 6 (factor + 1)  kp = factor      mid[n, c] = X[n, c] + disp[n, c] * s
+ *                                                                          child[n, j, c] = mid[n, c] + (disp[n, 6 + 6 j + c] * g) * s
+ *   first_refine and include_center  dw = 6 factor        kp = factor - 1  as above, and the rows mid[n] follow all the children
+ *   Child (n, j) is output row n kp + j; R = rows kp (+ rows).  c = 0..2 are the position, 3..5 the normal (not renormalised).
+ *   bbox[s] = {mn, mx}: the minimum and maximum over the sample's R output positions, per axis (a NaN takes no part).
+ *   mode 0 (normalize)  ctr = (mx + mn) / 2;  L = max over the axes of (mx - mn);  p = (child - ctr) / L * 0.99f
+ *   mode 1 (scale)      p = child / scale / 2
+ *   points = min(max(p / 1.2f + 0.5f, 0), 0.99f);  normals = the child's channels 3..5.
+ *   flag[0] |= 1 for a non-finite child position (tested explicitly: fminf drops a NaN), |= 2 for L == 0 in mode 0.
+ *   Outputs: points, normals (b, R, 3), bbox (b, 2, 3).  partials (b, T, 6) f32 is scratch, T = ceil(R / slide_refine_span(0)).
+ *   Two launches over (tile, sample): every workgroup stores the minimum and maximum of its tile of slide_refine_span(0) rows (a wave
+ *   reduction, then LDS; plain stores); then every workgroup reduces its sample's partials and transforms its tile.  A thread owns one
+ *   output row and reads its six displacements as three 8-byte words. */
+SLIDE_API int slide_refine_span(int level); /* level 0: the output rows of one tile; -2 otherwise */
+SLIDE_API int slide_refine_to_dpsr(int b, int m, int ldx, int dw, int rows, const float *X, const float *disp, int factor, int first_refine,
+                                   int include_center, float out_scale, int mode, float scale, float *points, float *normals,
+                                   float *bbox, float *partials, int *flag, slide_stream_t stream);
 
 /* ------------------------------------------------------------------ Part 3: denoiser engine */
 /* see slide_engine.h */

@@ -1,8 +1,10 @@
 """Point clouds -> DPSR indicator grids: the coordinate transformations of the reference's pointnet2/dpsr_evaluation.py
-(shapenet_psr_normalize lines 22-32, compute_center_and_max_length 34-43, the tail of network_output_to_dpsr_grid 77-86), and DPSR
-grids -> meshes on disk, optionally reduced to their largest connected component, and the point sets sampled from them
-(batch_mc_from_psr 291-340).  The refine-and-upsample network in front of
-them and the evaluation loop behind them are not part of this build."""
+(shapenet_psr_normalize lines 22-32, compute_center_and_max_length 34-43, the tail of network_output_to_dpsr_grid 77-86), the
+refinement network's output -> DPSR grids (network_output_to_dpsr_grid 46-86: point_upsample, normalise, clamp in two launches of
+slide_amd/refine.py, bit-equal to the reference's torch expressions), and DPSR grids -> meshes on disk, optionally reduced to their
+largest connected component, and the point sets sampled from them (batch_mc_from_psr 291-340).  The loop that drives them over a file
+of generated clouds (visualize_per_rank 176-289) is sampling_and_inference/mesh_reconstruction.py; the training-time evaluation
+(evaluate_per_rank) and the autoencoder branch are not part of this build."""
 import os
 
 import numpy as np
@@ -33,6 +35,24 @@ def points_to_dpsr_grid(points, normals, dpsr, scale=1, explicit_normalize=False
         points = points / scale / 2
     points = torch.clamp(points / 1.2 + 0.5, min=0, max=0.99).contiguous()
     return dpsr(points, normals.contiguous()), points, normals
+
+
+def network_output_to_dpsr_grid(X, displacement, dpsr, scale, pointnet_config, last_dim_as_indicator=False,
+                                only_original_points_split=False, explicit_normalize=False):
+    """X (B, npoints, 6) CUDA float, xyz + normals (7 with last_dim_as_indicator: +1 / -1 marks original / mirrored points, and with
+    only_original_points_split only the first half, the original points, is split); displacement (B, npoints, 6 k), the refinement
+    network's output; pointnet_config gives point_upsample_factor, first_refine_coarse_points,
+    include_displacement_center_to_final_output and output_scale_factor.  -> the reference's triple (psr_grid = dpsr(points, normals),
+    the refined points in [0, 0.99] as DPSR saw them, the refined normals).  ValueError for a non-finite refined point or, with
+    explicit_normalize, a sample whose refined points coincide (the reference returns NaN grids)."""
+    from slide_amd.refine import refine_to_dpsr_points
+    points, normals, _ = refine_to_dpsr_points(
+        X, displacement, pointnet_config["point_upsample_factor"],
+        first_refine_coarse_points=pointnet_config.get("first_refine_coarse_points", False),
+        include_displacement_center_to_final_output=pointnet_config.get("include_displacement_center_to_final_output", False),
+        output_scale_factor=pointnet_config.get("output_scale_factor", 0.001), scale=scale, explicit_normalize=explicit_normalize,
+        last_dim_as_indicator=last_dim_as_indicator, only_original_points_split=only_original_points_split)
+    return dpsr(points, normals), points, normals
 
 
 def batch_mc_from_psr(psr_grid, save_dir, save_prefix, batch_info=None, start_idx=0, sample_points_from_mesh=False,

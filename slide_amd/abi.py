@@ -196,6 +196,9 @@ PROTOTYPES = {name: _proto(args) for name, args in {
     "slide_mesh_cc_stats": "iqqppp" + "pppppppp" + "p",
     "slide_mesh_cc_select": "iqqppp" + "ppp" + "iqi" + "ppp" + "p",
     "slide_mesh_cc_compact": "iqq" + "ppp" + "pp" + "pp" + "pp" + "pppp" + "p",
+    "slide_refine_span": "i",
+    "slide_mirror_concat": "iiipiippppp",
+    "slide_refine_to_dpsr": "iiiii" + "pp" + "iii" + "fif" + "pppppp",
     "slide_hip_device_ok": "",
     "slide_lane_reduce_selftest": "pppip",
     "slide_philox_normal_selftest": "iiiiiipp",

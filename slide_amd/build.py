@@ -31,7 +31,7 @@ SOURCES = [("point_ops.hip", ["-ffp-contract=off"]), ("chamfer.hip", ["-ffp-cont
            ("occupancy_grid.hip", ["-ffp-contract=off"]), ("emd_pairwise.hip", ["-ffp-contract=off"]),
            ("dpsr.hip", ["-ffp-contract=off"]), ("dpsr_bwd.hip", ["-ffp-contract=off"]),
            ("marching_cubes.hip", ["-ffp-contract=off"]), ("mesh_sample.hip", ["-ffp-contract=off"]),
-           ("mesh_components.hip", ["-ffp-contract=off"]),
+           ("mesh_components.hip", ["-ffp-contract=off"]), ("refine_front.hip", ["-ffp-contract=off"]),
            ("engine.hip", UNROLL + NO_ATOMIC_OPT), ("gemm_ring.hip", UNROLL), ("attn_tail.hip", UNROLL),
            ("attn_tail_split.hip", UNROLL), ("gemm_gx.hip", UNROLL), ("pair_norm.hip", UNROLL), ("sa_chain.hip", UNROLL),
            ("gemm_gxs.hip", UNROLL), ("point_chain.hip", UNROLL), ("rows_ops.hip", []), ("train_ops.hip", []), ("encoder_ops.hip", []),

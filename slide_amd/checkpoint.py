@@ -26,3 +26,11 @@ def load_denoiser_state(hp, ckpt=None, ema_idx=1, seed=0):
             raise ValueError("parameter %s has shape %s, expected %s" % (name, t.shape, shape))
         out[name] = t
     return out
+
+
+def load_model_state_dict(ckpt):
+    """the `model_state_dict` of a reference checkpoint as {name: CPU tensor} (module-path models: net.load_state_dict(...))"""
+    ck = torch.load(ckpt, map_location="cpu")
+    if "model_state_dict" not in ck:
+        raise KeyError("%s has no model_state_dict" % ckpt)
+    return {k: v.detach().cpu() for k, v in ck["model_state_dict"].items()}

@@ -1,4 +1,4 @@
-"""The two latent-DDPM network configurations BASELINE.json names, as plain dict builders.
+"""The two latent-DDPM network configurations BASELINE.json names and the refine-and-upsample configuration, as plain dict builders.
 
 Same keys / values as the `pointnet_config` section of the reference's shipped JSON configs
 (pointnet2/configs/shapenet_psr_configs/ddpm_keypoint_training_configs/config_standard_attention_batchsize_32_s3_
@@ -45,6 +45,24 @@ def feature_ddpm_config():
                                           "model_output_scale_factor": 1.0, "loss_type": None,
                                           "keypoint_position_loss_weight": 0.0, "feature_loss_weight": 1.0,
                                           "keypoint_conditional": True}}
+
+
+def refine_and_upsample_config():
+    """The refinement network in front of DPSR with the symmetry prior (the reference's shipped .../refine_and_upsample_configs/
+    config_refine_and_upsample_standard_attention_s3_noise_0.02_symmetry.json, lists restored): 4096 mirrored and tagged points
+    (xyz + normal + tag) -> 6 x 5 displacements per point, no timestep, class-conditioned; DPSR at 128^3, sigma 2.  For the timing
+    tool and the tests: sampling_and_inference/mesh_reconstruction.py reads the JSON itself."""
+    hp = _pointnet_config("shapenet_dpsr_upsample_10_noise_0.02_symmetry", 4, 6, [32, 64, 128, 256, 512], [128, 128, 256, 256, 512])
+    hp["include_t"] = False
+    hp["architecture"].update({"npoint": [1024, 256, 64, 16], "radius": [0.1, 0.2, 0.4, 0.8], "nsample": [32, 32, 32, 32], "K": 8})
+    hp.update({"point_upsample_factor": 5, "first_refine_coarse_points": False, "include_displacement_center_to_final_output": False,
+               "output_scale_factor": 0.001})
+    return {"pointnet_config": hp,
+            "train_config": {"task": "upsample", "dataset": "shapenet_psr_dataset", "loss_type": "mse", "conditioned_on_cloud": False},
+            "dpsr_config": {"grid_res": 128, "psr_sigma": 2, "psr_tanh": True, "mirror_before_upsampling": True,
+                            "only_original_points_split": False},
+            "shapenet_psr_dataset_config": {"dataset": "shapenet_psr_dataset", "npoints": 2048, "scale": 1, "batch_size": 32,
+                                            "eval_batch_size": 32, "augmentation": {"noise_magnitude": 0.02}}}
 
 
 # label ids = sorted ShapeNet synset ids (pointnet2/shapenet_psr_dataloader/shapenet_psr_dataset.py:59-66)
