@@ -779,28 +779,38 @@ def _mesh_offsets(off, rows, name, dev):
     return torch.tensor(off, device=dev, dtype=torch.int64), len(off) - 1
 
 
-def _mesh_arrays(verts, faces, voff, foff):
-    verts = _chk_f32_cuda(verts, "verts", 2)
+def _mesh_faces(faces, voff, foff, nv, verts=None):
+    """the face and offset checks of every packed-mesh entry point -> (faces, voff, foff as device tensors, b); verts: the caller's
+    (sum V, 3) tensor when it has one -- its shape then joins the shape check, and nv = its rows"""
     if not isinstance(faces, torch.Tensor) or not faces.is_cuda:
         raise RuntimeError("faces must be a CUDA tensor")
     _chk_int(faces, "faces")
     faces = faces.contiguous()
-    if verts.size(1) != 3 or faces.dim() != 2 or faces.size(1) != 3:
-        raise ValueError("packed meshes are verts (sum V, 3) and faces (sum F, 3), got %s and %s" % (tuple(verts.shape), tuple(faces.shape)))
-    if faces.size(0) > 2 ** 31 - 1:
-        raise ValueError("at most 2^31 - 1 faces per call")
-    vo, b = _mesh_offsets(voff, verts.size(0), "voff", verts.device)
-    fo, bf = _mesh_offsets(foff, faces.size(0), "foff", verts.device)
+    faces_ok = faces.dim() == 2 and faces.size(1) == 3
+    if verts is None:
+        if not faces_ok:
+            raise ValueError("packed faces are (sum F, 3), got %s" % (tuple(faces.shape),))
+        if nv > 2 ** 31 - 1 or faces.size(0) > 2 ** 31 - 1:
+            raise ValueError("at most 2^31 - 1 vertices and faces per call")
+    else:
+        if verts.size(1) != 3 or not faces_ok:
+            raise ValueError("packed meshes are verts (sum V, 3) and faces (sum F, 3), got %s and %s" % (tuple(verts.shape), tuple(faces.shape)))
+        if faces.size(0) > 2 ** 31 - 1:
+            raise ValueError("at most 2^31 - 1 faces per call")
+    dev = faces.device if verts is None else verts.device
+    vo, b = _mesh_offsets(voff, nv, "voff", dev)
+    fo, bf = _mesh_offsets(foff, faces.size(0), "foff", dev)
     if b != bf:
         raise ValueError("voff and foff describe %d and %d meshes" % (b, bf))
-    return verts, faces, vo, fo, b
+    return faces, vo, fo, b
 
 
 def mesh_face_cdf(verts, faces, voff, foff):
     """slide_mesh_face_cdf on packed meshes: verts (sum V, 3) f32 and faces (sum F, 3) int32 CUDA tensors (vertex indices local to the
     mesh), voff / foff (b + 1) HOST offsets -> (areas (sum F,) f32, cdf (sum F,) int64 holding the uint64 sums, voff, foff as device
     tensors).  ValueError after one read of the flag word for a face index out of its mesh's range or a non-finite vertex of a face."""
-    verts, faces, vo, fo, b = _mesh_arrays(verts, faces, voff, foff)
+    verts = _chk_f32_cuda(verts, "verts", 2)
+    faces, vo, fo, b = _mesh_faces(faces, voff, foff, verts.size(0), verts)
     nf = faces.size(0)
     areas = torch.empty(nf, device=verts.device, dtype=torch.float32)
     cdf = torch.empty(nf, device=verts.device, dtype=torch.int64)
@@ -885,19 +895,9 @@ def mesh_cc_label(faces, voff, foff, nv, group=None, max_rounds=None):
     info = dict(rounds, reads, issued)).  ValueError for a face index outside [0, V) of its mesh (tested on the device before it is
     used; the status words are read once per `group` rounds); RuntimeError beyond max_rounds (default: the largest V + 1, which
     always suffices)."""
-    if not isinstance(faces, torch.Tensor) or not faces.is_cuda:
-        raise RuntimeError("faces must be a CUDA tensor")
-    _chk_int(faces, "faces")
-    faces = faces.contiguous()
-    if faces.dim() != 2 or faces.size(1) != 3:
-        raise ValueError("packed faces are (sum F, 3), got %s" % (tuple(faces.shape),))
-    nv, nf, dev = int(nv), faces.size(0), faces.device
-    if nv > 2 ** 31 - 1 or nf > 2 ** 31 - 1:
-        raise ValueError("at most 2^31 - 1 vertices and faces per call")
-    vo, b = _mesh_offsets(voff, nv, "voff", dev)
-    fo, bf = _mesh_offsets(foff, nf, "foff", dev)
-    if b != bf:
-        raise ValueError("voff and foff describe %d and %d meshes" % (b, bf))
+    nv = int(nv)
+    faces, vo, fo, b = _mesh_faces(faces, voff, foff, nv)
+    nf, dev = faces.size(0), faces.device
     if b > MESH_SAMPLE_MAX_BATCH:
         raise ValueError("at most %d meshes per call" % MESH_SAMPLE_MAX_BATCH)
     if nf and not nv:

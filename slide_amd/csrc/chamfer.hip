@@ -2,7 +2,7 @@
 //
 // Two launches per metric call:
 //   chamfer_nn_kernel      nearest neighbour (K = 1) of every valid point of x in y AND of every valid point of y in x, one
-//                          launch for both directions.  Same distance recipe as point_ops.hip (sqdist3, -ffp-contract=off), the
+//                          launch for both directions.  The shared distance recipe (kernel_util.h sqdist3; -ffp-contract=off), the
 //                          search set scanned in index order with a strict `<`: the result is the (distance, index)-lexicographic
 //                          minimum, bit-equal to slide_knn_points(K = 1) (ties -> lower index).
 //   chamfer_reduce_kernel  per cloud and direction: sum d, sum sqrt d, count d < threshold and, with per-point features, the
@@ -19,28 +19,10 @@
 #include <stdint.h>
 
 #include "../../include/slide_hip.h"
-
-#define LAUNCH_STATUS() ((int)hipGetLastError())
+#include "kernel_util.h"
+#include "launch.h"
 
 namespace {
-
-__device__ __forceinline__ float sqdist3(float ax, float ay, float az, float bx, float by, float bz) {
-  const float dx = ax - bx, dy = ay - by, dz = az - bz;
-  return fmaf(dz, dz, fmaf(dy, dy, dx * dx));  // the recipe of point_ops.hip (bit-equal distances)
-}
-
-// The XCD-aware block map of point_ops.hip's search kernels: block L runs on XCD L % 8 and takes the cloud pairs b = 8 k + L % 8,
-// so every tile of one pair -- both directions -- runs on one XCD and each private L2 fetches the pair once.
-struct SearchBlock { int b, tile; bool valid; };
-__device__ __forceinline__ SearchBlock search_block(int nb, int tiles) {
-  const int L = blockIdx.x, x = L & 7, q = L >> 3;
-  SearchBlock r;
-  r.tile = q % tiles;
-  r.b = (q / tiles) * 8 + x;
-  r.valid = r.b < nb;
-  return r;
-}
-static inline unsigned search_grid(int nb, int tiles) { return (unsigned)(8 * ((nb + 7) / 8) * tiles); }
 
 __device__ __forceinline__ int clamp_len(const int64_t *lengths, int b, int n) {
   if (!lengths) return n;

@@ -19,22 +19,10 @@
 #include <stdint.h>
 
 #include "../../include/slide_train.h"
-
-#define LAUNCH_STATUS() ((int)hipGetLastError())
+#include "kernel_util.h"
+#include "launch.h"
 
 namespace {
-
-// the XCD-aware block map of chamfer.hip: every tile of one cloud pair -- both directions -- runs on one XCD
-struct TileBlock { int b, tile; bool valid; };
-__device__ __forceinline__ TileBlock tile_block(int nb, int tiles) {
-  const int L = blockIdx.x, x = L & 7, q = L >> 3;
-  TileBlock r;
-  r.tile = q % tiles;
-  r.b = (q / tiles) * 8 + x;
-  r.valid = r.b < nb;
-  return r;
-}
-static inline unsigned tile_grid(int nb, int tiles) { return (unsigned)(8 * ((nb + 7) / 8) * tiles); }
 
 constexpr int BW_NT = 256;              // threads per workgroup
 constexpr int BW_TPT = 2;               // targets per thread: one broadcast LDS read feeds 2 x 64 x 4 pairs per wave
@@ -81,7 +69,7 @@ __global__ __launch_bounds__(BW_NT) void chamfer_cd_bwd_kernel(int nb, int n1, i
                                                                float *__restrict__ dx, float *__restrict__ dy) {
   __shared__ int4 tile[BW_TILE / 4];
   const int t1 = dx ? (n1 + BW_TQ - 1) / BW_TQ : 0, t2 = dy ? (n2 + BW_TQ - 1) / BW_TQ : 0;
-  const TileBlock tb = tile_block(nb, t1 + t2);
+  const SearchBlock tb = search_block(nb, t1 + t2);  // every tile of one cloud pair -- both directions -- on one XCD
   if (!tb.valid) return;
   const int b = tb.b, tid = threadIdx.x;
   const bool rev = tb.tile >= t1;  // the targets are y's points
@@ -177,7 +165,7 @@ template <int FM>
 int launch_bwd(int b, int n1, int n2, int f, const float *x, int sx, const float *y, int sy, const float *d1, const int64_t *i1,
                const float *d2, const int64_t *i2, const float *dred, float *dx, float *dy, hipStream_t stream) {
   const int tiles = (dx ? (n1 + BW_TQ - 1) / BW_TQ : 0) + (dy ? (n2 + BW_TQ - 1) / BW_TQ : 0);
-  hipLaunchKernelGGL(chamfer_cd_bwd_kernel<FM>, dim3(tile_grid(b, tiles)), dim3(BW_NT), 0, stream, b, n1, n2, f, x, sx, y, sy, d1, i1,
+  hipLaunchKernelGGL(chamfer_cd_bwd_kernel<FM>, dim3(search_grid(b, tiles)), dim3(BW_NT), 0, stream, b, n1, n2, f, x, sx, y, sy, d1, i1,
                      d2, i2, dred, dx, dy);
   return LAUNCH_STATUS();
 }

@@ -11,21 +11,16 @@
 //     entry is bit-equal to chamfer_reduce(chamfer_nn(x[i], y[j])) and does not depend on m, n, the pair's position or `symmetric`;
 //   * symmetric form (y is x): pairs j < i exit at once; pair (i, j) also stores its mirror out[j, i, d] = out[i, j, 1 - d] (the same
 //     two searches seen from the other cloud).  The diagonal is computed like any other pair.
-// Same distance recipe as chamfer.hip / point_ops.hip (sqdist3, -ffp-contract=off).  The norm expansion |a|^2 + |b|^2 - 2 a.b (and
+// The shared distance recipe (kernel_util.h sqdist3; the file is built with -ffp-contract=off).  The norm expansion |a|^2 + |b|^2 - 2 a.b (and
 // with it any MFMA form) is excluded: it is not bit-equal and cancels badly for near points.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/slide_hip.h"
-
-#define LAUNCH_STATUS() ((int)hipGetLastError())
+#include "kernel_util.h"
+#include "launch.h"
 
 namespace {
-
-__device__ __forceinline__ float sqdist3(float ax, float ay, float az, float bx, float by, float bz) {
-  const float dx = ax - bx, dy = ay - by, dz = az - bz;
-  return fmaf(dz, dz, fmaf(dy, dy, dx * dx));  // the recipe of point_ops.hip / chamfer.hip (bit-equal distances)
-}
 
 constexpr int PW_NT = 256;     // threads per workgroup (the reduction order depends on it: chamfer_reduce_kernel's RD_NT)
 constexpr int PW_TILE = 1024;  // search points per LDS tile, as three coordinate planes (12 KB)

@@ -7,7 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define LAUNCH_STATUS() ((int)hipGetLastError())
+#include "launch.h"
 
 namespace {
 

@@ -28,9 +28,8 @@
 #include <stdint.h>
 
 #include "../../include/slide_hip.h"
+#include "kernel_util.h"
 #include "launch.h"
-
-#define LAUNCH_STATUS() ((int)hipGetLastError())
 
 namespace {
 
@@ -54,11 +53,6 @@ struct EmdLds {
   V *remainL, *ratioL;      // per point of xyz1
   V *remainR, *ratioR;      // per point of xyz2
 };
-
-__device__ __forceinline__ float sqdist3(float ax, float ay, float az, float bx, float by, float bz) {
-  const float dx = ax - bx, dy = ay - by, dz = az - bz;
-  return fmaf(dz, dz, fmaf(dy, dy, dx * dx));  // the recipe of chamfer_pairwise.hip: identical points are at distance 0 exactly
-}
 
 __device__ __forceinline__ float fma_v(float a, float b, float c) { return fmaf(a, b, c); }
 __device__ __forceinline__ double fma_v(double a, double b, double c) { return fma(a, b, c); }

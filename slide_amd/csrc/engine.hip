@@ -5,17 +5,12 @@
 // units is declared in launch.h, which is also the map of which file defines what.
 #include "gemm_common.h"
 #include "ddpm_update.h"
+#include "kernel_util.h"
 #include "launch.h"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------ points
-__device__ __forceinline__ float sqdist3(float ax, float ay, float az, float bx, float by, float bz) {
-#pragma clang fp contract(off)
-  const float dx = ax - bx, dy = ay - by, dz = az - bz;
-  return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-}
-
 // Per sample (16 latent points): split x into xyz + features [x[3:], xyz] (attach_position_to_input_feature,
 // pointnet2_with_pcld_condition.py:332-346) and build the full 16x16 neighbour table sorted by
 // (squared distance, index) -- the K=16 and K=8 queries of every SA / FP level are prefixes of it

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "../../../include/experiments/slide_resident.h"
+#include "../kernel_util.h"
 #include "../launch.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -74,12 +75,6 @@ __device__ __forceinline__ float philox_normal(uint32_t seed_lo, uint32_t seed_h
   const float u1 = ((float)(c0 >> 8) + 0.5f) * (1.0f / 16777216.0f);
   const float u2 = ((float)(c1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
   return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-}
-
-__device__ __forceinline__ float sqdist3(float ax, float ay, float az, float bx, float by, float bz) {
-#pragma clang fp contract(off)
-  const float dx = ax - bx, dy = ay - by, dz = az - bz;
-  return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
 }
 
 // descriptor records are read through the CONSTANT address space: uniform index -> s_load into SGPRs (through the generic

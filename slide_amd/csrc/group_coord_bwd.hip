@@ -21,8 +21,7 @@
 #include <stdint.h>
 
 #include "../../include/slide_train.h"
-
-#define LAUNCH_STATUS() ((int)hipGetLastError())
+#include "launch.h"
 
 namespace {
 

@@ -1,6 +1,6 @@
 // launch.h -- what crosses translation units inside the library (internal: not part of the C ABI under include/): the launch
-// entry points that one .hip defines and another calls, the experiments-only status, and the per-device first-use helper of the
-// dynamic-LDS limit.  Every .hip that defines or calls one of these functions includes this header, so a drifted signature fails
+// entry points that one .hip defines and another calls, the experiments-only status, LAUNCH_STATUS() of every file that launches
+// by itself, and the per-device first-use helper of the dynamic-LDS limit.  Every .hip that defines or calls one of these functions includes this header, so a drifted signature fails
 // to compile in the defining file (the library is also linked with --no-undefined: a forgotten source fails the link).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -8,6 +8,9 @@
 #include "../../include/slide_engine.h"
 
 struct GemmArgs;  // gemm_common.h
+
+// what an entry point returns after its last launch: 0, or the HIP error of a launch that was refused
+#define LAUNCH_STATUS() ((int)hipGetLastError())
 
 // Status of an op whose kernel only exists in the EXPERIMENTS build (slide_amd/build.py: libslide_hip_exp.so, -DSLIDE_EXPERIMENTS):
 // the opt-in variants that lost their A/Bs (X-stationary tiles, per-point layer chains, head + update launch, wide / eight-wave

@@ -32,9 +32,9 @@
 #include <stdint.h>
 
 #include "../../include/slide_hip.h"
+#include "kernel_util.h"
+#include "launch.h"
 #include "marching_cubes_table.h"
-
-#define LAUNCH_STATUS() ((int)hipGetLastError())
 
 namespace {
 
@@ -54,36 +54,6 @@ struct Dims {
 };
 
 inline Dims dims_of(int r) { return Dims{r, (r + BI - 1) / BI, (r + BJ - 1) / BJ, (r + BK - 1) / BK}; }
-
-// inclusive prefix over the 64 lanes of a wave
-__device__ __forceinline__ int wave_incl_scan(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
-// exclusive prefix of v over the workgroup in thread order (NW waves); total = the workgroup's sum.  part: NW ints of LDS.
-template <int NW>
-__device__ __forceinline__ int block_excl_scan(int v, int *part, int &total) {
-  const int incl = wave_incl_scan(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();  // (part may still be read from an earlier call)
-  if ((threadIdx.x & 63) == 63) part[w] = incl;
-  __syncthreads();
-  int before = 0, sum = 0;
-#pragma unroll
-  for (int q = 0; q < NW; ++q) {
-    const int p = part[q];
-    before += (q < w) ? p : 0;
-    sum += p;
-  }
-  total = sum;
-  return before + incl - v;
-}
 
 template <int MODE>
 __global__ __launch_bounds__(NTB) void mc_brick_kernel(Dims d, int nbricks, const float *__restrict__ phi, float level,

@@ -22,15 +22,15 @@
 //
 // Counts: cnt_v[root]++, cnt_f[root of the face's first index]++ with int32 atomic adds, aggregated over the lanes of a wave that
 // share a root (a mesh's big component would otherwise take every lane's add on one address).
-// Per mesh, ONE workgroup of SCAN_NT threads, in passes of SCAN_TILE elements (SCAN_ITEMS consecutive ones per thread, wave scan +
-// wave totals in LDS, as mesh_cdf_kernel): rank of the roots (cid), C, counts by cid; selection by a maximum over the key
+// Per mesh, ONE workgroup of SCAN_NT threads, in passes of SCAN_TILE elements (SCAN_ITEMS consecutive ones per thread, then
+// kernel_util.h block_excl_scan, as mesh_cdf_kernel): rank of the roots (cid), C, counts by cid; selection by a maximum over the key
 // (size << 32 | 2^31 - 1 - root); exclusive scans of the vertex and face keep flags.  Nothing assumes that V fits in LDS.
 // Compaction: one launch over vertices and faces.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/slide_hip.h"
-
-#define LAUNCH_STATUS() ((int)hipGetLastError())
+#include "kernel_util.h"
+#include "launch.h"
 
 namespace {
 
@@ -43,17 +43,6 @@ constexpr int SCAN_TILE = SCAN_NT * SCAN_ITEMS;     // 4096 per pass
 constexpr int ST_ROUND_CAP = -5;
 
 typedef unsigned long long u64;
-
-// the mesh of packed row x: the last m with off[m] <= x (meshes may be empty: equal offsets)
-__device__ __forceinline__ int mesh_of(const long long *__restrict__ off, int b, long long x) {
-  int lo = 0, hi = b;  // off[lo] <= x < off[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= x) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
 
 __device__ __forceinline__ bool in_range(int i, long long nv) { return i >= 0 && i < nv; }
 
@@ -158,35 +147,6 @@ __global__ __launch_bounds__(CC_NT) void cc_count_kernel(int b, long long nv, lo
   }
 }
 
-__device__ __forceinline__ int wave_incl_scan(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
-// one pass of the workgroup: the number of flagged elements of the mesh in front of this thread's SCAN_ITEMS; `run` (the same in
-// every thread) advances by the pass's total
-__device__ __forceinline__ int pass_excl_scan(int sum, int *part, int &run) {
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int incl = wave_incl_scan(sum);
-  __syncthreads();  // (part is still read by the pass before)
-  if (lane == 63) part[w] = incl;
-  __syncthreads();
-  int before = run, total = 0;
-#pragma unroll
-  for (int k = 0; k < SCAN_NT / 64; ++k) {
-    const int p = part[k];
-    before += (k < w) ? p : 0;
-    total += p;
-  }
-  run += total;
-  return before + incl - sum;
-}
-
 __global__ __launch_bounds__(SCAN_NT) void cc_rank_kernel(const long long *__restrict__ voff, const int *__restrict__ L,
                                                           const int *__restrict__ cnt_v, const int *__restrict__ cnt_f, int *rank,
                                                           int *__restrict__ cid, int *__restrict__ nverts, int *__restrict__ nfaces,
@@ -205,7 +165,9 @@ __global__ __launch_bounds__(SCAN_NT) void cc_rank_kernel(const long long *__res
       root[k] = (x0 + k < nv) && l[x0 + k] == x0 + k;
       sum += root[k];
     }
-    int c = pass_excl_scan(sum, part, run);
+    int total;  // c: the number of flagged elements of the mesh in front of this thread's SCAN_ITEMS
+    int c = block_excl_scan<SCAN_NT / 64>(sum, part, total, run);
+    run += total;
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k)
       if (root[k]) {
@@ -230,7 +192,6 @@ __global__ __launch_bounds__(SCAN_NT) void cc_select_kernel(const int *__restric
   const int m = blockIdx.x;
   const long long v0 = voff[m], nv = voff[m + 1] - v0, f0 = foff[m], nf = foff[m + 1] - f0;
   const int *l = L + v0;
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // a component is a candidate when it has a face and its size reaches min_size
   auto candidate_size = [&](int r) -> long long {
     const int nfc = cnt_f[v0 + r];
@@ -246,13 +207,7 @@ __global__ __launch_bounds__(SCAN_NT) void cc_select_kernel(const int *__restric
         const long long size = candidate_size((int)v);
         if (size >= 1) best = max(best, ((u64)size << 32) | (u64)(0x7fffffff - (int)v));
       }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) best = max(best, (u64)__shfl_xor((long long)best, d, 64));
-    if (lane == 0) wbest[w] = best;
-    __syncthreads();
-    best = 0;
-#pragma unroll
-    for (int q = 0; q < SCAN_NT / 64; ++q) best = max(best, wbest[q]);
+    best = block_reduce<SCAN_NT / 64>(best, wbest, MaxOf());
     if (best) best_root = 0x7fffffff - (int)(best & 0xffffffffu);
   }
   // 2. kept vertices
@@ -270,7 +225,9 @@ __global__ __launch_bounds__(SCAN_NT) void cc_select_kernel(const int *__restric
       }
       sum += keep[k];
     }
-    int c = pass_excl_scan(sum, part, run);
+    int total;  // c: the number of flagged elements of the mesh in front of this thread's SCAN_ITEMS
+    int c = block_excl_scan<SCAN_NT / 64>(sum, part, total, run);
+    run += total;
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k)
       if (x0 + k < nv) vnew[v0 + x0 + k] = keep[k] ? c++ : -1;
@@ -292,7 +249,9 @@ __global__ __launch_bounds__(SCAN_NT) void cc_select_kernel(const int *__restric
       }
       sum += keep[k];
     }
-    int c = pass_excl_scan(sum, part, run);
+    int total;  // c: the number of flagged elements of the mesh in front of this thread's SCAN_ITEMS
+    int c = block_excl_scan<SCAN_NT / 64>(sum, part, total, run);
+    run += total;
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k)
       if (x0 + k < nf) fnew[f0 + x0 + k] = keep[k] ? c++ : -1;

@@ -39,8 +39,8 @@
 // 20480-sample launch (profiles/mesh_sampling.md).
 #include "ddpm_update.h"
 #include "../../include/slide_hip.h"
-
-#define LAUNCH_STATUS() ((int)hipGetLastError())
+#include "kernel_util.h"
+#include "launch.h"
 
 namespace {
 
@@ -74,17 +74,6 @@ __device__ __forceinline__ float length3(const float (&n)[3]) {
   return sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
 }
 
-// the mesh of packed row x: the last m with off[m] <= x (meshes may be empty: equal offsets)
-__device__ __forceinline__ int mesh_of(const long long *__restrict__ off, int b, long long x) {
-  int lo = 0, hi = b;  // off[lo] <= x < off[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= x) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(AREA_NT) void mesh_area_kernel(int b, long long nf, const float *__restrict__ verts,
                                                             const int *__restrict__ faces, const long long *__restrict__ voff,
                                                             const long long *__restrict__ foff, float *__restrict__ areas,
@@ -113,16 +102,6 @@ __global__ __launch_bounds__(AREA_NT) void mesh_area_kernel(int b, long long nf,
   if (bad) atomicOr(flag, bad);
 }
 
-__device__ __forceinline__ u64 wave_incl_scan64(u64 v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const u64 o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
 // q of one area; scale = (double)amax, 0 when the mesh has no positive finite area
 __device__ __forceinline__ u64 quantise(float area, double amax) {
   if (!(area > 0.0f) || !(area < INFINITY) || !(amax > 0.0)) return 0;
@@ -137,7 +116,6 @@ __global__ __launch_bounds__(CDF_NT) void mesh_cdf_kernel(const long long *__res
   if (nf <= 0) return;
   const float *ar = areas + f0;
   u64 *out = cdf + f0;
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
 
   // 1. the largest finite area.  Areas are >= 0, and non-negative floats order like their bit patterns.
   unsigned mx = 0;
@@ -145,14 +123,7 @@ __global__ __launch_bounds__(CDF_NT) void mesh_cdf_kernel(const long long *__res
     const float a = ar[x];
     if (a < INFINITY) mx = max(mx, __float_as_uint(a));
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, d, 64));
-  if (lane == 0) wmax[w] = mx;
-  __syncthreads();
-  mx = 0;
-#pragma unroll
-  for (int q = 0; q < CDF_NT / 64; ++q) mx = max(mx, wmax[q]);
-  const double amax = (double)__uint_as_float(mx);
+  const double amax = (double)__uint_as_float(block_reduce<CDF_NT / 64>(mx, wmax, MaxOf()));
 
   // 2. quantise and scan, CDF_TILE faces per pass
   u64 run = 0;
@@ -165,7 +136,10 @@ __global__ __launch_bounds__(CDF_NT) void mesh_cdf_kernel(const long long *__res
       q[k] = (x0 + k < nf) ? quantise(ar[x0 + k], amax) : 0;
       sum += q[k];
     }
-    const u64 incl = wave_incl_scan64(sum);
+    // kernel_util.h block_excl_scan<CDF_NT / 64>(sum, part, total, run), written out: through the helper (any inlined form of
+    // it) the register allocator takes 80 VGPRs for this kernel instead of 66 and the resource table drops from 7 to 6 waves/SIMD
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const u64 incl = wave_incl_scan(sum);
     __syncthreads();  // (part is still read by the pass before)
     if (lane == 63) part[w] = incl;
     __syncthreads();

@@ -10,7 +10,7 @@
 //
 // The nearest rule, in fp32 with contraction off (build.py: -ffp-contract=off; the fmaf calls below are the only fused steps):
 //     d32(p, c) = fmaf(dz, dz, fmaf(dy, dy, dx * dx)),  dx = fl(p.x - axis[i]), dy = fl(p.y - axis[j]), dz = fl(p.z - axis[k])
-//   (the distance recipe of chamfer.hip / point_ops.hip).
+//   (the distance recipe, kernel_util.h sqdist3, split across the loops below: dxx, dxy).
 //   1. Lattice step.  Per axis: index 0 when p <= axis[0], R - 1 when p >= axis[R - 1]; else the bracket axis[lo] <= p < axis[lo + 1]
 //      is found by bisection and lo + 1 is taken only when |fl(p - axis[lo + 1])| < |fl(p - axis[lo])| (an exact midpoint keeps the
 //      lower index).  Every rounding step of d32 is monotone, so the cell (i*, j*, k*) of the three per-axis results attains the
@@ -32,8 +32,7 @@
 #include <stdint.h>
 
 #include "../../include/slide_hip.h"
-
-#define LAUNCH_STATUS() ((int)hipGetLastError())
+#include "launch.h"
 
 namespace {
 

@@ -3,21 +3,16 @@
 // Written for CDNA4: 64-wide wavefronts, one workgroup per (batch element, tile of queries) instead of
 // the reference's one-block-per-batch-element launches, coalesced channel-minor traffic, LDS-staged
 // search sets.  Index semantics are bit-exact with oracle/ops_cpu.c (which restates
-// _ext-src/src/*.cu); distances use the shared recipe fmaf(dz,dz,fmaf(dy,dy,dx*dx)) and this file is
+// _ext-src/src/*.cu); distances use the shared recipe fmaf(dz,dz,fmaf(dy,dy,dx*dx)) (kernel_util.h sqdist3) and this file is
 // compiled with -ffp-contract=off so nothing else is contracted.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/slide_hip.h"
-
-#define LAUNCH_STATUS() ((int)hipGetLastError())
+#include "kernel_util.h"
+#include "launch.h"
 
 namespace {
-
-__device__ __forceinline__ float sqdist3(float ax, float ay, float az, float bx, float by, float bz) {
-  const float dx = ax - bx, dy = ay - by, dz = az - bz;
-  return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-}
 
 // ---------------------------------------------------------------------------------------------- gather
 // out[b,c,j] = points[b,c,idx[b,j]]   (_ext-src/src/sampling_gpu.cu:8-20)
@@ -220,23 +215,6 @@ __global__ __launch_bounds__(1024) void fps_kernel_large(int n, int m, int bs, i
     if (tid == 0) idxs[j] = old;
   }
 }
-
-// ---------------------------------------------------------------------------------------------- search kernels: block map
-// XCD-aware (batch element, query tile) map of the search kernels (round 6; VERDICT r5 item 9: ball_query moved 6.5x its algorithmic
-// bytes at n = 8192).  Every workgroup of a batch element streams that element's WHOLE search set; consecutive workgroup ids go to
-// consecutive XCDs (MI355X_MICROARCH.md: block b runs on XCD b % 8 -- relied on for speed only), so with a (tile, b) grid the eight
-// query tiles of an element ran on eight XCDs and each private L2 fetched the set once more.  Here the grid is linear and id L ->
-// XCD L % 8 takes the elements b = 8 k + L % 8: all query tiles of an element run on ONE XCD and its set is fetched once.
-struct SearchBlock { int b, tile; bool valid; };
-__device__ __forceinline__ SearchBlock search_block(int nb, int tiles) {
-  const int L = blockIdx.x, x = L & 7, q = L >> 3;
-  SearchBlock r;
-  r.tile = q % tiles;
-  r.b = (q / tiles) * 8 + x;
-  r.valid = r.b < nb;
-  return r;
-}
-static inline unsigned search_grid(int nb, int tiles) { return (unsigned)(8 * ((nb + 7) / 8) * tiles); }
 
 // ---------------------------------------------------------------------------------------------- ball query
 // ball_query_gpu.cu:9-47

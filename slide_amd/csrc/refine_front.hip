@@ -18,8 +18,8 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/slide_hip.h"
-
-#define LAUNCH_STATUS() ((int)hipGetLastError())
+#include "kernel_util.h"
+#include "launch.h"
 
 namespace {
 
@@ -140,16 +140,21 @@ __device__ __forceinline__ void refine_row(const RefineArgs &a, int smp, long lo
   for (int c = 0; c < 6; ++c) ch[c] = base[c] + (d[c] * a.g) * a.s;
 }
 
-__device__ __forceinline__ float wave_min(float v) {
+// the waves' minima / maxima of xyz into red[0 .. 3) / red[3 .. 6), behind ONE barrier; slot row r < 3 folds with MinOf, the others
+// with MaxOf (kernel_util.h: fminf / fmaxf, which drop a NaN)
+__device__ __forceinline__ void minmax_to_slots(const float (&mn)[3], const float (&mx)[3], float (*red)[RF_WAVES]) {
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
-  return v;
+  for (int k = 0; k < 3; ++k) {
+    const float lo = wave_reduce(mn[k], MinOf()), hi = wave_reduce(mx[k], MaxOf());
+    if ((threadIdx.x & 63) == 0) {
+      red[k][threadIdx.x >> 6] = lo;
+      red[3 + k][threadIdx.x >> 6] = hi;
+    }
+  }
+  __syncthreads();
 }
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-  return v;
+__device__ __forceinline__ float fold_minmax_row(const float (*red)[RF_WAVES], int r) {
+  return r < 3 ? fold_slots<RF_WAVES>(red[r], MinOf()) : fold_slots<RF_WAVES>(red[r], MaxOf());
 }
 
 // grid (tiles, b): partials[smp][tile] = {min xyz, max xyz} of the tile's rows
@@ -165,25 +170,8 @@ __global__ __launch_bounds__(RF_NT) void refine_minmax_kernel(RefineArgs a, floa
 #pragma unroll
     for (int k = 0; k < 3; ++k) mn[k] = mx[k] = ch[k];  // (fminf / fmaxf below drop a NaN; launch 2 reports it)
   }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    mn[k] = wave_min(mn[k]);
-    mx[k] = wave_max(mx[k]);
-  }
-  if ((t & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      red[k][t >> 6] = mn[k];
-      red[3 + k][t >> 6] = mx[k];
-    }
-  }
-  __syncthreads();
-  if (t < 6) {
-    float v = red[t][0];
-#pragma unroll
-    for (int w = 1; w < RF_WAVES; ++w) v = t < 3 ? fminf(v, red[t][w]) : fmaxf(v, red[t][w]);
-    partials[((size_t)smp * gridDim.x + tile) * 6 + t] = v;
-  }
+  minmax_to_slots(mn, mx, red);
+  if (t < 6) partials[((size_t)smp * gridDim.x + tile) * 6 + t] = fold_minmax_row(red, t);
 }
 
 // grid (tiles, b): every workgroup reduces its sample's partials (written by the launch before), then transforms its tile
@@ -201,35 +189,13 @@ __global__ __launch_bounds__(RF_NT) void refine_apply_kernel(RefineArgs a, int m
       mx[k] = fmaxf(mx[k], ps[(size_t)q * 6 + 3 + k]);
     }
   }
+  minmax_to_slots(mn, mx, red);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    mn[k] = wave_min(mn[k]);
-    mx[k] = wave_max(mx[k]);
+    mn[k] = fold_slots<RF_WAVES>(red[k], MinOf());
+    mx[k] = fold_slots<RF_WAVES>(red[3 + k], MaxOf());
   }
-  if ((t & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      red[k][t >> 6] = mn[k];
-      red[3 + k][t >> 6] = mx[k];
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    mn[k] = red[k][0];
-    mx[k] = red[3 + k][0];
-#pragma unroll
-    for (int w = 1; w < RF_WAVES; ++w) {
-      mn[k] = fminf(mn[k], red[k][w]);
-      mx[k] = fmaxf(mx[k], red[3 + k][w]);
-    }
-  }
-  if (tile == 0 && t < 6) {
-    float v = red[t][0];
-#pragma unroll
-    for (int w = 1; w < RF_WAVES; ++w) v = t < 3 ? fminf(v, red[t][w]) : fmaxf(v, red[t][w]);
-    bbox[smp * 6 + t] = v;
-  }
+  if (tile == 0 && t < 6) bbox[smp * 6 + t] = fold_minmax_row(red, t);
   float ctr[3], L = 0.f;
   if (mode == 0) {
     float len[3];

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "../../include/slide_train.h"
+#include "launch.h"
 
 namespace {
 
@@ -329,8 +330,6 @@ __global__ __launch_bounds__(256) void attn_rows_bwd_kernel(int K, int C, int ld
     ds[(pt * K + k) * lds + c] = w * (vv - o) * d;
   }
 }
-
-#define LAUNCH_STATUS() ((int)hipGetLastError())
 
 }  // namespace
 
